@@ -20,9 +20,16 @@ leaf dedup, default; --no-leaf-dedup evaluates every leaf in its own row as the
 reference's InferenceWorker does): the searches are bit-identical either way
 (tests/test_gpu_engine.py), and the line reports nn.rows beside nn.leaves.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        torchrun --nproc-per-node N bench.py --gpus N ...
-Prints ONE JSON line on rank 0.  Without torchrun, --gpus N > 1 starts the N rank processes itself
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, W warm-up plies, K
+timed plies (with the in-run kernel timers and clock sampling the rooflines of the line read), the line.
+--full adds the measurements that take runs of their own: the CPU baseline before the GPU is touched
+(--cpu-seconds, --no-cpu-baseline), the no-cache and no-dedup twins after the timed region (--twin-no-cache,
+--twin-no-dedup) and, with --secondary, the other trunk dtype on a fresh engine.  --dump-outputs DIR writes
+what the last timed ply handed its caller as DIR/<name>.npy (dump_outputs below); the games, seeds and network
+are fixed by the arguments, so two builds run with the same arguments can be compared array for array.
+Without torchrun, --gpus N > 1 starts the N rank processes itself
 (before this process touches the GPU) with torchrun's environment, one per GPU; it refuses N ranks
 on fewer visible GPUs unless SPMCTS_ALLOW_OVERSUBSCRIBE=1 (a rehearsal; with SPMCTS_DIST_BACKEND=gloo,
 since RCCL refuses two ranks on one GPU).
@@ -297,6 +304,30 @@ def cpu_baseline(seconds, cores, sims, filter_factor, num_blocks, threads=1, ope
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write `arrays` (name -> numpy array) as path/<name>.npy, float64 for float64 and 64-bit integer data
+    (exact below 2**53), float32 for the rest; at most `budget` bytes in all: an array over its equal share of
+    the budget is cut to a fixed sample of its rows (numpy RandomState(seed), rows kept in order), the same rows
+    in every run.  Returns name -> shape written."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    shapes = {}
+    for name, a in sorted(arrays.items()):
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype.itemsize == 8 else np.float32)
+        if a.nbytes > share:
+            keep = max(1, share // max(1, a[0].nbytes))
+            a = a[np.sort(np.random.RandomState(seed).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -308,8 +339,17 @@ def main():
     ap.add_argument("--filter-factor", type=int, default=32)
     ap.add_argument("--blocks", type=int, default=20)
     ap.add_argument("--bucket", type=int, default=256)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own beside the headline: the CPU baseline (--cpu-seconds, "
+                         "--no-cpu-baseline), the twins after the timed region (--twin-no-cache, --twin-no-dedup) and, "
+                         "with --secondary, the other trunk dtype.  Off by default: a plain run sets up, warms up, "
+                         "times --steps plies and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed plies write what the last of them handed its caller as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB): the ply's (games finished, records exported), the Move "
+                         "records of the games it finished, and every game slot's id and ply count after it")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: seconds of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-gather", action="store_true", help="skip the rank-0 Move gather")
     ap.add_argument("--exchange-every", type=int, default=8,
                     help="plies per episode-batch exchange round (Move rows to rank 0 + stats all-reduce)")
@@ -334,14 +374,14 @@ def main():
     ap.add_argument("--no-pack", action="store_true",
                     help="lanes > 1: keep round-aligned tower tiles (no SPMCTS_TOWER_PACK)")
     ap.add_argument("--twin-no-dedup", type=int, default=5, metavar="PLIES",
-                    help="after the timed region, turn leaf dedup off and time PLIES more plies of the same games "
+                    help="with --full: after the timed region, turn leaf dedup off and time PLIES more plies of the same games "
                          "(every leaf its own row, as the reference): reported as no_dedup_twin")
     ap.add_argument("--eval-cache", type=int, default=1, metavar="PLIES",
                     help="evaluation cache window (include/spmcts.h spmcts_set_eval_cache): a position evaluated in "
                          "the last PLIES plies takes the cached outputs instead of a network row; 1 (default) = "
                          "within the ply, so every output a timed ply uses was computed in that ply; 0 = off")
     ap.add_argument("--twin-no-cache", type=int, default=5, metavar="PLIES",
-                    help="with --eval-cache: after the timed region time PLIES more plies with the cache off "
+                    help="with --full and --eval-cache: after the timed region time PLIES more plies with the cache off "
                          "(per-step leaf dedup alone): reported as no_cache_twin")
     ap.add_argument("--no-clock", action="store_true",
                     help="do not sample the gfx clock (amdsmi) during the timed region")
@@ -351,7 +391,7 @@ def main():
                     help="element type of the fused trunk's weights / activations (fp32 accumulation); fp16 (the "
                          "default) is the reference's own inference dtype (amp.autocast, inference_worker.py:117)")
     ap.add_argument("--secondary", action="store_true",
-                    help="also time the other trunk dtype (bf16 <-> fp16) on a fresh engine with the same seeds, "
+                    help="with --full: also time the other trunk dtype (bf16 <-> fp16) on a fresh engine with the same seeds, "
                          "--warmup and --steps, reported as secondary_dtype.  Off by default: the headline runs the "
                          "reference's inference dtype (fp16) alone; bf16's search shift is bounded at 0.02 "
                          "(tests/test_gpu_statistical.py SHIFT_TOL), eight times fp16's error")
@@ -361,6 +401,8 @@ def main():
                          "(mcts.py:328-331), 4 in its headline self-play setup (InferenceProxy workers, "
                          "SURVEY §6); 1 = sequential search (bit-exact to the reference's sequential fixtures)")
     args = ap.parse_args()
+    if args.secondary and not args.full:
+        ap.error("--secondary times a second engine: it runs with --full only")
     arena_mode = args.mode == "arena"
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -378,11 +420,11 @@ def main():
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={os.environ['WORLD_SIZE']}; the launched ranks count",
               file=sys.stderr, flush=True)
 
-    # The CPU baseline runs FIRST, in child processes started before this process touches the GPU
+    # The CPU baseline (--full) runs FIRST, in child processes started before this process touches the GPU
     # (children of a GPU-initialised process must not exec); rank 0 of a 1-process run only.
     env_rank, env_world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     cpu = None
-    if env_rank == 0 and env_world == 1 and not args.no_cpu_baseline and not arena_mode:
+    if args.full and env_rank == 0 and env_world == 1 and not args.no_cpu_baseline and not arena_mode:
         cpu = cpu_baseline(args.cpu_seconds, min(16, os.cpu_count() or 1), args.sims, args.filter_factor, args.blocks,
                            threads=args.search_threads)
 
@@ -425,10 +467,17 @@ def main():
     # finished games' Move rows: staged on each rank's device, gathered to rank 0 once per episode
     # batch (every --exchange-every plies, and once more at the end of the timed region) together
     # with the episode statistics (distributed.MoveExchange); a single process hands them on at once
-    ex = D.MoveExchange(42, 7, sink=lambda g: gathered.append(int(g["z"].shape[0])), every=args.exchange_every)
+    last = {"moves": [], "ply": (0, 0)}  # --dump-outputs: what the latest ply handed its caller (references only)
+
+    def sink(g):
+        gathered.append(int(g["z"].shape[0]))
+        last["moves"].append(g)
+
+    ex = D.MoveExchange(42, 7, sink=sink, every=args.exchange_every)
 
     def one_step():
-        eng.ply(on_moves=ex.stage if not (args.no_gather or arena_mode) else None)
+        last["moves"] = []
+        last["ply"] = eng.ply(on_moves=ex.stage if not (args.no_gather or arena_mode) else None)
         # statistics are read (a host sync on the device counters) only for a real exchange round
         ex.end_ply(eng.stats_vector if D.is_distributed() else None)
 
@@ -467,6 +516,29 @@ def main():
 
     c1 = eng.counters()
     eng.check()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed ply as its caller saw it: ply()'s return value, the Move records on_moves received (the
+        # lanes' in lane order; under a process group the last exchange round's, all ranks'), and the game slots
+        # it left behind (lane after lane): each slot's game id and ply count, which every move chosen and every
+        # game finished in the run so far have shaped
+        import numpy as np
+
+        arrays = {"ply_finished_exported": np.array(last["ply"], dtype=np.float64)}
+        if not (args.no_gather or arena_mode):
+            keys = {"state": (0, 42), "tree_probs": (0, 7), "q": (0,), "q_f64": (0,), "z": (0,), "game": (0,)}
+            for k, empty in keys.items():
+                parts = [g[k].cpu().numpy() for g in last["moves"]]
+                arrays["moves_" + k] = np.concatenate(parts) if parts else np.zeros(empty, dtype=np.float32)
+            # the export ring's record order is the order the games' blocks reached it: sort the records by
+            # (game id, stones on the board), unique per record, so two runs list them alike
+            order = np.lexsort((np.abs(arrays["moves_state"]).sum(1), arrays["moves_game"]))
+            for k in keys:
+                arrays["moves_" + k] = arrays["moves_" + k][order]
+        gs = [e.arena.games_state() for e in getattr(eng, "lanes", [eng])]
+        arrays["slots_game_id"] = np.concatenate([g["game_id"] for g in gs])
+        arrays["slots_ply"] = np.concatenate([g["ply"] for g in gs]).astype(np.float32)
+        dumped = dump_outputs(args.dump_outputs, arrays)
     moves_local = c1["moves"] - c0["moves"]
     # per-rank lines (an all_gather on every rank): stragglers and exchange cost show in a scaling record
     per_rank = D.rank_report([moves_local / elapsed if elapsed else 0.0, elapsed, ex.rounds,
@@ -684,6 +756,8 @@ def main():
                                      f"games per GPU, policy ResNet-{4 * args.filter_factor}x{args.blocks} (seed 0) vs "
                                      f"opponent (seed 1), evaluate mode (temp/20, noise on), no Move records")
     out["cpu_baseline"] = cpu
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
 
     def twin(plies):
         """`plies` more plies on the same arenas right after the timed region: (the headline's unit per second --
@@ -707,7 +781,7 @@ def main():
         return (t_moves / t_el, t_el / plies * 1e3,
                 (t_c1["nn_rows"] - t_c0["nn_rows"]) / max(1, t_c1["nn_leaves"] - t_c0["nn_leaves"]))
 
-    if args.twin_no_cache > 0 and getattr(eng, "eval_cache", 0):
+    if args.full and args.twin_no_cache > 0 and getattr(eng, "eval_cache", 0):
         for e in getattr(eng, "lanes", [eng]):
             e.arena.set_eval_cache(0)
             e.eval_cache = 0
@@ -716,7 +790,7 @@ def main():
             "plies": args.twin_no_cache, "value": v_, "unit": out["unit"], "ms_per_step": ms_, "rows_per_leaf": rpl_,
             "note": "the plies right after the timed region, evaluation cache off (spmcts_set_eval_cache 0): leaf "
                     "dedup within each simulation step only"}
-    if args.twin_no_dedup > 0 and getattr(eng, "leaf_dedup", False):
+    if args.full and args.twin_no_dedup > 0 and getattr(eng, "leaf_dedup", False):
         # the same arenas, right after the timed region: every leaf gets its own network row
         for e in getattr(eng, "lanes", [eng]):
             e.arena.set_leaf_dedup(False)
@@ -727,7 +801,7 @@ def main():
             "plies": args.twin_no_dedup, "value": v_, "unit": out["unit"], "ms_per_step": ms_, "rows_per_leaf": rpl_,
             "note": "the plies right after the timed region, leaf dedup off (spmcts_set_leaf_dedup): every leaf "
                     "evaluated in its own row, as the reference's InferenceWorker"}
-    if args.secondary and not arena_mode:
+    if args.full and args.secondary and not arena_mode:
         # the other trunk element type (bf16 <-> fp16) on a FRESH engine with the same seeds, warm-up and
         # timed plies as the headline (games of the same age, so the two lines compare like for like);
         # `value` is the --dtype line.  The headline arenas are released first.

@@ -1,5 +1,5 @@
 """CPU-baseline calibration (build container only; needs /root/reference): the reference's OWN self-play
-pipeline timed next to bench.py's cpu_baseline leg (the oracle "port") on the same host cores.
+pipeline timed next to bench.py --full's cpu_baseline leg (the oracle "port") on the same host cores.
 
     python scripts/ref_cpu_baseline.py [seconds] [cores]
 

@@ -970,7 +970,7 @@ def test_bench_line_small_with_no_dedup_twin():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--games", "512", "--sims", "16", "--blocks", "2",
-           "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--twin-no-dedup", "2", "--secondary"]
+           "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline", "--twin-no-dedup", "2", "--secondary"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=root, check=True).stdout
     line = [l for l in out.splitlines() if l.startswith("{")]
     assert len(line) == 1
@@ -999,7 +999,7 @@ def test_bench_line_small_with_eval_cache():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--games", "512", "--sims", "16", "--blocks", "2",
-           "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--eval-cache", "2", "--twin-no-cache", "2",
+           "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline", "--eval-cache", "2", "--twin-no-cache", "2",
            "--twin-no-dedup", "2"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=root, check=True).stdout
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][0])
@@ -1019,10 +1019,52 @@ def test_bench_arena_line_with_eval_cache():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--mode", "arena", "--games", "256", "--sims", "16",
-           "--blocks", "2", "--steps", "6", "--warmup", "6", "--no-cpu-baseline", "--twin-no-cache", "4",
+           "--blocks", "2", "--steps", "6", "--warmup", "6", "--full", "--no-cpu-baseline", "--twin-no-cache", "4",
            "--twin-no-dedup", "0"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=root, check=True).stdout
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][0])
     assert d["unit"] == "games/s" and d["config"]["eval_cache_plies"] == 1 and d["nn"]["cache_rows"] > 0
     tw = d["no_cache_twin"]
     assert tw["unit"] == "games/s" and tw["value"] >= 0 and d["nn"]["rows_per_leaf"] < tw["rows_per_leaf"] <= 1.0
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain bench.py run (no --full) prints the headline line alone -- no CPU baseline, twins or secondary
+    dtype -- with --steps timed plies and their ms_per_step, and --dump-outputs writes the last timed ply's
+    outputs as float32 / float64 .npy files under 64 MB that a second run with the same arguments repeats
+    value for value."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for name in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--games", "256", "--sims", "16",
+               "--blocks", "2", "--steps", "3", "--warmup", "20", "--dump-outputs", str(tmp_path / name)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=root, check=True).stdout
+        line = [l for l in out.splitlines() if l.startswith("{")]
+        assert len(line) == 1
+        d = json.loads(line[0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "fp16"
+        assert d["unit"] == "positions/s" and d["higher_is_better"] is True
+        # --steps plies were timed: every game slot moves once per ply
+        assert round(d["value"] * d["ms_per_step"] * 3 / 1e3) == 3 * 256
+        assert d["cpu_baseline"] is None
+        assert not {"no_cache_twin", "no_dedup_twin", "secondary_dtype"} & set(d)
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == sorted(k + ".npy" for k in d["dumped_outputs"])
+        dumps.append({f: np.load(tmp_path / name / f) for f in files})
+    a, b = dumps
+    assert {"ply_finished_exported.npy", "moves_state.npy", "moves_tree_probs.npy", "moves_z.npy", "slots_ply.npy",
+            "slots_game_id.npy"} <= set(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64), f
+        assert a[f].shape == b[f].shape and np.array_equal(a[f], b[f]), f
+    # after 20 + 3 plies some of the 256 games have ended: the last ply exported their Move records
+    n = a["moves_z.npy"].shape[0]
+    assert n > 0 and a["ply_finished_exported.npy"][1] == n and a["moves_state.npy"].shape == (n, 42)
+    assert np.allclose(a["moves_tree_probs.npy"].sum(1), 1.0, atol=1e-5)
+    assert a["slots_ply.npy"].shape == (256,) and a["slots_game_id.npy"].shape == (256,)
