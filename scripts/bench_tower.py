@@ -38,8 +38,7 @@ if args.trunk_only:
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / args.iters
-    print(json.dumps(dict(batch=args.batch, dtype=args.dtype, cg=os.environ.get("SPMCTS_TOWER_CG"), trunk_ms=ms,
-                          tflops=fl / ms / 1e9)))
+    print(json.dumps(dict(batch=args.batch, dtype=args.dtype, trunk_ms=ms, tflops=fl / ms / 1e9)))
     sys.exit(0)
 for name, ev in (("hip", HipTowerEvaluator(net)), ("hip_fusedheads", HipTowerEvaluator(net, fused_heads=True)),
                  ("hip_torchheads", HipTowerEvaluator(net, fused_heads=False)),

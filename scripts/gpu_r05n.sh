@@ -1,4 +1,4 @@
-# Round 5: per-launch LDS copies of the child blocks in the threaded tree kernels (BlockCache: levels read
+# Round 5: per-launch LDS copies of the child blocks in the threaded tree kernels (since removed: levels read
 # LDS, no fence between sims).  (1) The bit-exact threaded parity tests and the engine tests; (2) Philox-mode
 # games identical to round 4's library (scripts/rng_equal.py); (3) isolated tree kernels on steady-state
 # trees, alternated with round 4's library; (4) the driver-form bench, alternated.

@@ -1,7 +1,6 @@
 #!/bin/bash
-# Product device code before/after a source refactor (round 6: the Cfg::ABL ablations moved out of the product
-# k-loops into tower_abl.h / tower_m16_abl.h): the gfx950 assembly of one translation unit with the product
-# flags (no -DSPMCTS_AB), comments and debug directives stripped, compared with a saved copy.  Only the
+# Product device code before/after a source refactor that must leave the kernels as they are: the gfx950
+# assembly of one translation unit with the product flags (no -DSPMCTS_AB), comments and debug directives stripped, compared with a saved copy.  Only the
 # per-compilation __hip_cuid_* symbol may differ.  Runs on the build host (no GPU).
 #   scripts/product_isa_equal.sh save tower.hip /tmp/base.s     (before)
 #   scripts/product_isa_equal.sh cmp  tower.hip /tmp/base.s     (after)

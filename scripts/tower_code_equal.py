@@ -1,5 +1,5 @@
-"""Bit-equality of a timing alternative (SPMCTS_TOWER_CG) with the default trunk: run once per code
-(the switch is read once per process) writing the host-path outputs, then compare the files.
+"""Bit-equality of a trunk alternate of the A/B library (SPMCTS_TOWER_C256=3) or of two builds with the default
+trunk: run once per setting (a switch is read once per process) writing the host-path outputs, then compare the files.
   python scripts/tower_code_equal.py dump OUT.npz [FILTER_FACTOR [bf16|fp16]]   |   python scripts/tower_code_equal.py cmp A.npz B.npz"""
 import sys
 

@@ -184,9 +184,7 @@ def lib():
 
 # environment switches read only by the A/B library (libspmcts_ab.so); the product library refuses them with
 # SPMCTS_ERR_AB_SWITCH (-5, include/spmcts.h) rather than silently ignoring them
-AB_SWITCHES = ("SPMCTS_TOWER_CG", "SPMCTS_TOWER_RING", "SPMCTS_TOWER_C256", "SPMCTS_WIDE_TAILS", "SPMCTS_HEADS",
-               "SPMCTS_HEADS_C256", "SPMCTS_TREE_BLOCK", "SPMCTS_EXPAND_CO", "SPMCTS_TOWER_M16",
-               "SPMCTS_TREE_COPIES", "SPMCTS_PEER_PUSH", "SPMCTS_CACHE_SHARE")
+AB_SWITCHES = ("SPMCTS_TOWER_C256", "SPMCTS_HEADS", "SPMCTS_HEADS_C256")
 ERR_AB_SWITCH = -5
 
 

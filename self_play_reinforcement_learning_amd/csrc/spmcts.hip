@@ -862,8 +862,9 @@ __device__ __forceinline__ TreeRoot load_root(const View &v, int tree) {
 }
 
 // The path of the sim in flight, in LDS (one group per tree): node ids and, per level, the node's n, vl
-// (this sim's virtual loss included) and w as this sim read them, and where the node's record sits (cs: a
-// BlockCache slot, kRootRegs for the root and the root's children, kUncached).  One wave owns the tree, so
+// (this sim's virtual loss included) and w as this sim read them, and where the node's record sits (cs:
+// kRootRegs for the root and the root's children, kept in registers; kUncached = global memory only).  One wave
+// owns the tree, so
 // nothing changes them between the read and this sim's backup: a terminal backup writes n + 1, w + value,
 // vl - 1 from here instead of reading the nodes again (one memory round trip less per terminal sim).
 struct PathLds {
@@ -872,125 +873,27 @@ struct PathLds {
 };
 enum { kUncached = -1, kRootRegs = -2 };
 
-// Per-launch LDS copies of the child blocks a tree's sims read (round 5).  One wave owns a tree for the
-// whole launch, so a block's record, copied in from global memory the first time a level reads it, stays
-// exact as long as every store the launch makes to the block is made to the copy as well (write-through:
-// the global record stays current for later launches).  A level that hits reads LDS instead of issuing a
-// dependent global load, and a sim whose stores all went to copied blocks or to the root and its children
-// (kept in registers for the launch, TreeRoot) needs no fence before the next sim: nothing it wrote is read
-// back from global memory in this launch.  With the copies full, stores to uncopied blocks set `dirty`,
-// and the next global read of node records waits on a workgroup fence first (round 4's per-sim fence).
-// The copies hold everything a level reads (n, vl, child block, p, w, the valid mask); the strong-play
-// flag is written to global memory only (nothing in a launch reads it).
-template <int P, int S>
-struct BlockCache {
-  static constexpr int BYTES = NodeRec<P>::BYTES;
-  int32_t *tag;  // [S] tree-local block index of each copy (16-byte aligned)
-  char *rec;     // [S][BYTES] the copies
-  int cnt = 0;   // copies in use (group-uniform)
-  bool dirty = false;  // stores to uncopied blocks since the last fence (group-uniform)
+// The stores a launch has issued to node records that live in global memory only (kUncached: every node but
+// the root and its children, which TreeRoot keeps in registers for the launch).  One wave owns a tree for the
+// whole launch, so a sim whose stores all went to the root and its children needs no fence before the next
+// sim: nothing it wrote is read back from global memory in this launch.  A store to any other node sets
+// `dirty`, and the next global read of node records waits on a workgroup fence first -- a fence only after
+// issued stores, instead of one per sim.  (Per-launch LDS copies of the child blocks, written through, were
+// measured slower and removed: DESIGN.md §4.)
+struct StoreFence {
+  bool dirty = false;  // stores to kUncached nodes since the last fence (group-uniform)
   __device__ __forceinline__ void fence_if_dirty() {
     if (dirty) {
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       dirty = false;
     }
   }
-  // the slot holding block `blk` or kUncached; every lane may ask for its own block
-  __device__ __forceinline__ int find(int blk) const {
-    int hit = kUncached;
-    if constexpr (S > 0) {
-#pragma unroll
-      for (int i = 0; i < S / 4; ++i) {
-        if (4 * i >= cnt) break;
-        const int4 t = ((const int4 *)tag)[i];
-        if (t.x == blk && 4 * i + 0 < cnt) hit = 4 * i + 0;
-        if (t.y == blk && 4 * i + 1 < cnt) hit = 4 * i + 1;
-        if (t.z == blk && 4 * i + 2 < cnt) hit = 4 * i + 2;
-        if (t.w == blk && 4 * i + 3 < cnt) hit = 4 * i + 3;
-      }
-    }
-    return hit;
-  }
-  // copy block `blk` (global record `g`) into a free slot (group-uniform call); kUncached when full
-  __device__ __forceinline__ int insert(int blk, const char *g, int lane) {
-    if constexpr (S == 0) {
-      return kUncached;
-    } else {
-      if (cnt >= S) return kUncached;
-      fence_if_dirty();
-      const int s = cnt++;
-      const uint4 *src = (const uint4 *)(g + 32 * lane);  // P lanes x 32 bytes = the record
-      const uint4 a = src[0], b = src[1];
-      uint4 *dst = (uint4 *)(rec + s * BYTES + 32 * lane);
-      dst[0] = a;
-      dst[1] = b;
-      if (lane == 0) tag[s] = blk;
-      return s;
-    }
-  }
-  // a new block's copy from the values the caller stores to global memory (k_expand_vl); kUncached when full
-  __device__ __forceinline__ int insert_new(int blk, int lane, float p, uint32_t vm) {
-    if constexpr (S == 0) {
-      return kUncached;
-    } else {
-      if (cnt >= S) return kUncached;
-      const int s = cnt++;
-      char *r = rec + s * BYTES;
-      ((int32_t *)(r + NodeRec<P>::N))[lane] = 0;
-      ((int32_t *)(r + NodeRec<P>::VL))[lane] = 0;
-      ((int32_t *)(r + NodeRec<P>::C))[lane] = -1;
-      ((float *)(r + NodeRec<P>::PR))[lane] = p;
-      ((double *)(r + NodeRec<P>::W))[lane] = 0.0;
-      if (lane == 0) {
-        *(uint32_t *)(r + NodeRec<P>::VM) = vm;
-        tag[s] = blk;
-      }
-      return s;
-    }
-  }
-  template <class T>
-  __device__ __forceinline__ T &at(int s, int off, int a) const {
-    return ((T *)(rec + s * BYTES + off))[a];
-  }
-  __device__ __forceinline__ uint32_t vm(int s) const { return *(const uint32_t *)(rec + s * BYTES + NodeRec<P>::VM); }
 };
-
-#ifdef SPMCTS_TREE_PROF
-// Profiling build only (make prof: libspmcts_prof.so): shader-clock cycles per sim phase, summed over the
-// trees, per kernel (select: [0, 8), expand: [8, 16)) -- [0..5] the phases of TP_* below, [6] the largest
-// per-tree launch time, [7] the most sims one tree ran in one launch
-__device__ unsigned long long g_tprof[16];
-enum { TP_LOAD = 0, TP_SCORE = 1, TP_ARGMAX = 2, TP_LEAF = 3, TP_DESCEND = 4, TP_RNG = 5, TP_OTHER = 5 };
-#define TP_MARK(sc, i)                                 \
-  do {                                                 \
-    const unsigned long long t_ = clock64();           \
-    (sc).tp[i] += t_ - (sc).tlast;                     \
-    (sc).tlast = t_;                                   \
-  } while (0)
-#else
-#define TP_MARK(sc, i) \
-  do {                 \
-  } while (0)
-#endif
 
 // The tree's counters of one kernel launch (the same value in every lane of the group), added to the
 // arena's counters once at the end of the launch instead of a read-modify-write per sim.
 struct SimCnt {
   int64_t sims = 0, depth = 0, term = 0, leak = 0, nn = 0, hwm = 0;
-#ifdef SPMCTS_TREE_PROF
-  unsigned long long tp[6] = {0, 0, 0, 0, 0, 0}, tlast = 0, t0 = 0;
-  int64_t sims0 = 0;
-  __device__ void prof_begin() {
-    t0 = tlast = clock64();
-    sims0 = sims;
-  }
-  __device__ void prof_flush(int base) const {
-    const unsigned long long t1 = clock64();
-    for (int i = 0; i < 6; ++i) atomicAdd(&g_tprof[base + i], tp[i]);
-    atomicMax(&g_tprof[base + 6], t1 - t0);
-    atomicMax(&g_tprof[base + 7], (unsigned long long)(sims - sims0));
-  }
-#endif
   __device__ void flush(int64_t *cnt) const {
     cnt[C_SIMS] += sims;
     cnt[C_DEPTH] += depth;
@@ -1006,11 +909,11 @@ struct SimCnt {
 // q = (w - vl)/(n + vl) and u = c p sqrt(N + vl_parent)/(1 + n + vl) (mcts.py:59-78), pending leaves
 // locked (child-block index -2, score -1e10, mcts.py:86-88).  Returns SIM_PENDING with the leaf
 // locked and its path stashed in slot j, SIM_DONE for a terminal leaf (backed up, path vl removed),
-// SIM_LEAK for a leak, SIM_ERROR on a corrupt tree; R (the root in registers) and the block copies bc are
-// updated to match.  The return value is uniform across the group.
-template <class G, int S>
+// SIM_LEAK for a leak, SIM_ERROR on a corrupt tree; R (the root in registers) is updated to match and sf
+// records the stores issued.  The return value is uniform across the group.
+template <class G>
 __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng, bool &terr, const PathLds &pl,
-                      bool noise, double nz, SimCnt &sc, BlockCache<G::APAD, S> &bc) {
+                      bool noise, double nz, SimCnt &sc, StoreFence &sf) {
   constexpr int P = G::APAD;
   const int lane = threadIdx.x & (P - 1);
   const int gbase = (threadIdx.x & 63) & ~(P - 1);
@@ -1035,7 +938,6 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
       pl.vl[depth] = node_vl;
       pl.w[depth] = node_w;
       pl.cs[depth] = ncs;
-      if (ncs >= 0) bc.template at<int32_t>(ncs, NodeRec<P>::VL, node % P) = node_vl;
     }
     // the global store of the path's virtual loss waits for the sim's end (one store per path node, all
     // at once): gfx950's vmcnt counts stores too, so a store here would hold up the next level's loads.
@@ -1059,44 +961,23 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
       cc = R.cc;
       cvl = R.cvl;
     } else {
-      lcs = bc.find(cb);
-      if (lcs == kUncached) lcs = bc.insert(cb, nd_rec<P>(v, nb + (size_t)cb * P), lane);
-      if (lcs >= 0) {
-        vm = bc.vm(lcs);
-        if (lane < G::A) {
-          cn = bc.template at<int32_t>(lcs, NodeRec<P>::N, lane);
-          cw = bc.template at<double>(lcs, NodeRec<P>::W, lane);
-          cp = bc.template at<float>(lcs, NodeRec<P>::PR, lane);
-          cc = bc.template at<int32_t>(lcs, NodeRec<P>::C, lane);
-          cvl = bc.template at<int32_t>(lcs, NodeRec<P>::VL, lane);
-        }
-      } else {
-        bc.fence_if_dirty();
-        vm = nd_vm<P>(v, bb + cb);
-        const size_t ci = nb + (size_t)cb * P + lane;
-        if (lane < G::A) {
-          cn = nd_n<P>(v, ci);
-          cw = nd_w<P>(v, ci);
-          cp = nd_p<P>(v, ci);
-          cc = nd_c<P>(v, ci);
-          cvl = nd_vl<P>(v, ci);
-        }
+      lcs = kUncached;
+      sf.fence_if_dirty();
+      vm = nd_vm<P>(v, bb + cb);
+      const size_t ci = nb + (size_t)cb * P + lane;
+      if (lane < G::A) {
+        cn = nd_n<P>(v, ci);
+        cw = nd_w<P>(v, ci);
+        cp = nd_p<P>(v, ci);
+        cc = nd_c<P>(v, ci);
+        cvl = nd_vl<P>(v, ci);
       }
     }
-#ifdef SPMCTS_TREE_PROF
-    // (profiling: the loads completed before the jitter, to time the two apart)
-    if (cn == -12345 || cw == -1.5 || cp == -1.5f || cvl == -12345 || vm == 0xdeadbeefu) sc.tp[TP_OTHER] += 1;
-    TP_MARK(sc, TP_LOAD);
-#endif
     // the jitter does not depend on the child block: drawn here, it overlaps the loads above
     bool terr_j = false;
     const double jit = rng_group<G>(v, rng, lane, gbase, &terr_j);
     // valid (mcts.py:86-88): valid move and not locked by a pending sim
     const bool valid = (lane < G::A) && ((vm >> lane) & 1u) && cc != -2;
-#ifdef SPMCTS_TREE_PROF
-    if (jit == -1.5) sc.tp[TP_OTHER] += 1;
-    TP_MARK(sc, TP_RNG);
-#endif
     double score = -10000000000.0;
     if (valid) {
       // q (mcts.py:59-62): (w - vl) / (n + vl)
@@ -1113,7 +994,7 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
         nd_vl<P>(v, nb + pl.node[k]) = pl.vl[k];
         unc |= pl.cs[k] == kUncached;
       }
-      if (group_or<P>(unc)) bc.dirty = true;
+      if (group_or<P>(unc)) sf.dirty = true;
       sc.leak += 1;
       return SIM_LEAK;
     }
@@ -1121,13 +1002,11 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
     double s = -INFINITY;
     if (lane < G::A) s = score + 0.000001 * jit;
     rng_advance(v, rng, G::A);
-    TP_MARK(sc, TP_SCORE);
     int a = lane;
     int cc_a = cc, cn_a = cn, cvl_a = cvl;
     double cw_a = cw;
     group_argmax_carry<P>(s, a, cc_a, cn_a, cvl_a, cw_a);  // lane a's child fields in every lane
     const int child = cb * P + a;
-    TP_MARK(sc, TP_ARGMAX);
     if (cc_a < 0) {
       // leaf: _expand_node (mcts.py:301-321)
       Board nb2 = b;
@@ -1148,23 +1027,14 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
           nd_w<P>(v, idx) = w1;
           if (strong) nd_f<P>(v, idx) = 1;
           nd_vl<P>(v, idx) = vl1;
-          if (ck >= 0) {
-            bc.template at<int32_t>(ck, NodeRec<P>::N, nk % P) = n1;
-            bc.template at<double>(ck, NodeRec<P>::W, nk % P) = w1;
-            bc.template at<int32_t>(ck, NodeRec<P>::VL, nk % P) = vl1;
-          }
           unc |= ck == kUncached;
         }
         if (lane == 0) {
           nd_n<P>(v, nb + child) = cn_a + 1;
           nd_w<P>(v, nb + child) = cw_a + val;
           if (strong) nd_f<P>(v, nb + child) = 1;
-          if (lcs >= 0) {
-            bc.template at<int32_t>(lcs, NodeRec<P>::N, a) = cn_a + 1;
-            bc.template at<double>(lcs, NodeRec<P>::W, a) = cw_a + val;
-          }
         }
-        if (group_or<P>(unc) || lcs == kUncached) bc.dirty = true;
+        if (group_or<P>(unc) || lcs == kUncached) sf.dirty = true;
         R.n += 1;  // the root is path node 0
         R.vl -= 1;
         R.w += val;
@@ -1187,7 +1057,7 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
           nd_vl<P>(v, nb + nk) = pl.vl[k];
           unc |= pl.cs[k] == kUncached;
         }
-        if (group_or<P>(unc)) bc.dirty = true;
+        if (group_or<P>(unc)) sf.dirty = true;
       }
       sc.sims += 1;
       sc.depth += depth + 1;
@@ -1196,7 +1066,6 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
         if (!done) {
           // lock the leaf (mcts.py:359); the path was stashed above for the backup
           nd_c<P>(v, nb + child) = -2;
-          if (lcs >= 0) bc.template at<int32_t>(lcs, NodeRec<P>::C, a) = -2;
           v.plen[ps] = depth + 1;
           v.leaf[ps] = child;
           v.lpos[ps] = nb2.pos;
@@ -1205,9 +1074,8 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
           v.need[ps] = 1;
         }
       }
-      if (!done && lcs == kUncached) bc.dirty = true;
+      if (!done && lcs == kUncached) sf.dirty = true;
       if (!done && depth == 0 && lane == a) R.cc = -2;
-      TP_MARK(sc, TP_LEAF);
       return done ? SIM_DONE : SIM_PENDING;
     }
     if (depth == 0) a0 = a;
@@ -1220,7 +1088,6 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
     ncs = lcs;  // the child's record is in this level's block
     player = -player;
     ++depth;
-    TP_MARK(sc, TP_DESCEND);
     if (depth >= G::MAXD) {
       if (lane == 0) set_err(v, SPMCTS_ERR_STATE);
       return SIM_ERROR;
@@ -1230,45 +1097,35 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
 
 // Refill pending slot j: start sims until one waits for the network or the tree's budget of
 // search_node calls is spent (`started` counts them, mcts.py:328-331 submits `iterations`).  No fence
-// between sims: a sim reads what the previous one wrote from the block copies or the registers, and
-// the copies' `dirty` rule fences before any global read of node records after an uncopied store.
-template <class G, int S>
+// between sims: a sim reads the root and its children from the registers, and StoreFence's `dirty` rule fences
+// before any global read of node records after a store to one.
+template <class G>
 __device__ int fill_slot_vl(const View &v, int tree, int j, int limit, int &started, TreeRoot &R, TreeRng &rng,
-                            bool &terr, const PathLds &pl, bool noise, double nz, SimCnt &sc,
-                            BlockCache<G::APAD, S> &bc) {
+                            bool &terr, const PathLds &pl, bool noise, double nz, SimCnt &sc, StoreFence &sf) {
   while (started < limit) {
     ++started;
-    const int r = sim_vl<G, S>(v, tree, j, R, rng, terr, pl, noise, nz, sc, bc);
+    const int r = sim_vl<G>(v, tree, j, R, rng, terr, pl, noise, nz, sc, sf);
     if (r == SIM_PENDING || r == SIM_ERROR) return r;
   }
   return SIM_DONE;
 }
 
-// LDS block copies per tree: none in the shipped kernels.  Measured (profiles/r05/tree2/): with 16
-// copies per tree the isolated expand ran 250 -> 295-300 us and select unchanged (a launch starts with no
-// copies, so most blocks are copied once and read once; and the levels of a sim are a chain of short
-// dependent LDS / permute / FP64 latencies, not memory round trips: scripts/bench_tree.py --prof).
-// The A/B library keeps them behind SPMCTS_TREE_COPIES=1.
-template <int TB>
-constexpr int kCopies = 0;
-
-// First step of a search: fill the K slots of every searching tree.
-template <class G, int TB = 64, int S = kCopies<TB>>
-__global__ __launch_bounds__(TB) void k_select_vl(View v, int n_active) {
+// First step of a search: fill the K slots of every searching tree.  One wave of 64 threads: 64/P trees, a
+// P-lane group each.  (LDS copies of the child blocks a tree's sims read, 16 per tree, were measured slower --
+// the isolated expand 250 -> 295-300 us, select unchanged: a launch starts with no copies, so most blocks are
+// copied once and read once, and the levels of a sim are a chain of short dependent LDS / permute / FP64
+// latencies, not memory round trips -- and removed, as were workgroups of 2..8 waves: DESIGN.md §4.)
+template <class G>
+__global__ __launch_bounds__(64) void k_select_vl(View v, int n_active) {
   constexpr int P = G::APAD;
-  constexpr int GPB = TB / P;
-  constexpr int S1 = S > 0 ? S : 4;
+  constexpr int GPB = 64 / P;
   __shared__ int32_t s_node[GPB][G::MAXD], s_n[GPB][G::MAXD], s_vl[GPB][G::MAXD], s_cs[GPB][G::MAXD];
   __shared__ double s_w[GPB][G::MAXD];
-  __shared__ __attribute__((aligned(16))) int32_t s_tag[GPB][S1];
-  __shared__ __attribute__((aligned(16))) char s_rec[S > 0 ? GPB : 1][S > 0 ? S : 1][NodeRec<P>::BYTES];
   const int lane = threadIdx.x & (P - 1);
   const int grp = threadIdx.x / P;
   const PathLds pl{s_node[grp], s_n[grp], s_vl[grp], s_cs[grp], s_w[grp]};
-  BlockCache<P, S> bc;
-  bc.tag = s_tag[grp];
-  bc.rec = S > 0 ? &s_rec[grp][0][0] : nullptr;
-  const int slot = blockIdx.x * (int)(blockDim.x / P) + grp;  // blockDim = 64 (GPB trees) or P (one tree)
+  StoreFence sf;
+  const int slot = blockIdx.x * (int)(blockDim.x / P) + grp;  // blockDim = 64: GPB trees
   if (slot >= n_active) return;
   const int tree = v.active[slot];
   if (tree < 0) return;
@@ -1282,20 +1139,14 @@ __global__ __launch_bounds__(TB) void k_select_vl(View v, int n_active) {
   TreeRoot R = load_root<G>(v, tree);
   bool terr = false;
   SimCnt sc;
-#ifdef SPMCTS_TREE_PROF
-  sc.prof_begin();
-#endif
   const int kt = v.tK[tree];  // this tree's sims in flight (its own thread_count, <= K)
   for (int j = 0; j < kt; ++j) {
     if (v.need[tree * v.K + j]) continue;
     // SIM_ERROR (a corrupt tree: the sticky SPMCTS_ERR_STATE flag is set) ends the tree's launch; the counters
     // of the sims completed before it are still flushed below (the failing sim's path vl is not written)
-    if (fill_slot_vl<G, S>(v, tree, j, limit, started, R, rng, terr, pl, noise, nz, sc, bc) == SIM_ERROR) break;
+    if (fill_slot_vl<G>(v, tree, j, limit, started, R, rng, terr, pl, noise, nz, sc, sf) == SIM_ERROR) break;
   }
   if (lane == 0) {
-#ifdef SPMCTS_TREE_PROF
-    sc.prof_flush(0);
-#endif
     sc.flush(v.cnt + (size_t)tree * C_NCNT);
     v.tstarted[tree] = started;
     if (terr) set_err(v, SPMCTS_ERR_TAPE);
@@ -1804,36 +1655,16 @@ __global__ __launch_bounds__(64) void k_expand(View v, const float *probs0, cons
 // earlier slots of the same tree have changed the shared ancestors.  Pending leaves of trees that
 // are not searching (a _set_node expansion, slot 0, path length 0) are completed without a refill.
 // ----------------------------------------------------------------------------
-template <class G, int TB, int S>
-__device__ __forceinline__ void expand_vl_body(View v, const float *probs0, const float *values0,
-                                               const float *probs1, const float *values1);
-
-template <class G, int TB = 64, int S = kCopies<TB>>
-__global__ __launch_bounds__(TB) void k_expand_vl(View v, const float *probs0, const float *values0,
-                                                  const float *probs1, const float *values1) {
-  expand_vl_body<G, TB, S>(v, probs0, values0, probs1, values1);
-}
-
-// The same held to 96 registers (SPMCTS_EXPAND_CO=1, a timing variant): its waves then fit on a SIMD
-// beside a trunk wave (416 registers) instead of waiting for the trunk workgroup to retire, at the
-// price of register spills on the dependent chain.
+// (The body is a function of its own, inlined into the kernel: hipcc optimises it before it inlines it, and
+// written straight into the kernel the prefetch below lost its merged LDS stores.)
 template <class G>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void k_expand_vl_co(
-    View v, const float *probs0, const float *values0, const float *probs1, const float *values1) {
-  expand_vl_body<G, 64, 0>(v, probs0, values0, probs1, values1);
-}
-
-template <class G, int TB, int S>
 __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, const float *values0,
                                                const float *probs1, const float *values1) {
   constexpr int P = G::APAD;
-  constexpr int GPB = TB / P;
+  constexpr int GPB = 64 / P;
   constexpr int KMAX = P;  // slots whose records one lane each prefetches (spmcts_arena_create: K <= P)
-  constexpr int S1 = S > 0 ? S : 4;
   __shared__ int32_t s_node[GPB][G::MAXD], s_n[GPB][G::MAXD], s_vl[GPB][G::MAXD], s_cs[GPB][G::MAXD];
   __shared__ double s_w[GPB][G::MAXD];
-  __shared__ __attribute__((aligned(16))) int32_t s_tag[GPB][S1];
-  __shared__ __attribute__((aligned(16))) char s_rec[S > 0 ? GPB : 1][S > 0 ? S : 1][NodeRec<P>::BYTES];
   // the prefetched path nodes (k < P) and network outputs of each slot, per tree group; each LDS word
   // is written and later read by the same wave (LDS operations of a wave stay in order)
   __shared__ int32_t s_pnode[GPB][KMAX][P];
@@ -1845,9 +1676,7 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
   const int tree = (blockIdx.x * blockDim.x + threadIdx.x) / P;
   if (tree >= v.T) return;
   const PathLds pl{s_node[grp], s_n[grp], s_vl[grp], s_cs[grp], s_w[grp]};
-  BlockCache<P, S> bc;
-  bc.tag = s_tag[grp];
-  bc.rec = S > 0 ? &s_rec[grp][0][0] : nullptr;
+  StoreFence sf;
   const int K = v.K;
   const size_t nb = nbase<G>(v, tree);
   const size_t bb = (size_t)tree * v.cap;
@@ -1902,9 +1731,6 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
   }
   bool terr = false;
   SimCnt sc;
-#ifdef SPMCTS_TREE_PROF
-  sc.prof_begin();
-#endif
   // one copy of the slot body (a rolled loop: the unrolled form was 70 KB of code, more than the
   // instruction cache two CUs share, for a kernel that runs one wave per CU on a latency chain)
 #pragma unroll 1
@@ -1933,7 +1759,7 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
       }
       const double val = (double)s_vr[grp][j] * (double)mover;
       if (!refill) {
-        // no sims in this launch (nothing copied, the root not in registers): read-modify-write backup of the
+        // no sims in this launch (the root not in registers): read-modify-write backup of the
         // path (distinct nodes): one lane per path node, the node ids prefetched; a node's depth fixes its
         // lane, so the slots' updates of a shared ancestor are one lane's program order
         for (int k = lane; k < plen; k += P) {
@@ -1951,14 +1777,14 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       } else {
         // with sims in this launch: the root and its children from the registers (TreeRoot), deeper path
-        // nodes and the leaf from their block copies when copied (write-through), else read-modify-write in
-        // global memory after a fence if an uncopied store is outstanding (BlockCache)
+        // nodes and the leaf read-modify-write in global memory, after a fence if a store is outstanding
+        // (StoreFence: the new block's stores above are)
         if (lane == 0) nd_vm<P>(v, bb + blk) = vmnew;
-        if (bc.insert_new(blk, lane, pnew, vmnew) == kUncached) bc.dirty = true;
+        sf.dirty = true;
         const int a1 = plen > 1 ? s_pnode[grp][j][1] - R.cb * P : 0;  // path node 1: root child a1
         const int r1n = __shfl(R.cn, gbase + a1, 64), r1vl = __shfl(R.cvl, gbase + a1, 64);
         const double r1w = __shfl(R.cw, gbase + a1, 64);
-        bc.fence_if_dirty();
+        sf.fence_if_dirty();
         int unc = 0;
         for (int k = lane; k < plen; k += P) {
           const int nk = k < P ? s_pnode[grp][j][k] : v.pnode[(size_t)ps * G::MAXD + k];
@@ -1972,25 +1798,10 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
             nd_w<P>(v, idx) = r1w + val;
             nd_vl<P>(v, idx) = r1vl - 1;
           } else {
-            const int ck = bc.find(nk / P);
-            if (ck >= 0) {
-              int32_t &n = bc.template at<int32_t>(ck, NodeRec<P>::N, nk % P);
-              double &w = bc.template at<double>(ck, NodeRec<P>::W, nk % P);
-              int32_t &vl = bc.template at<int32_t>(ck, NodeRec<P>::VL, nk % P);
-              const int32_t n1 = n + 1, vl1 = vl - 1;
-              const double w1 = w + val;
-              n = n1;
-              w = w1;
-              vl = vl1;
-              nd_n<P>(v, idx) = n1;
-              nd_w<P>(v, idx) = w1;
-              nd_vl<P>(v, idx) = vl1;
-            } else {
-              nd_n<P>(v, idx) += 1;
-              nd_w<P>(v, idx) += val;
-              nd_vl<P>(v, idx) -= 1;
-              unc = 1;
-            }
+            nd_n<P>(v, idx) += 1;
+            nd_w<P>(v, idx) += val;
+            nd_vl<P>(v, idx) -= 1;
+            unc = 1;
           }
         }
         // the leaf: a root child (plen 1, registers: lane la), or a deeper node
@@ -2002,28 +1813,14 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
             nd_w<P>(v, nb + leaf) = R.cw + val;
           }
         } else {
-          const int cl = bc.find(leaf / P);  // group-uniform
           if (lane == 0) {
-            if (cl >= 0) {
-              bc.template at<int32_t>(cl, NodeRec<P>::C, leaf % P) = blk;
-              int32_t &n = bc.template at<int32_t>(cl, NodeRec<P>::N, leaf % P);
-              double &w = bc.template at<double>(cl, NodeRec<P>::W, leaf % P);
-              const int32_t n1 = n + 1;
-              const double w1 = w + val;
-              n = n1;
-              w = w1;
-              nd_c<P>(v, nb + leaf) = blk;
-              nd_n<P>(v, nb + leaf) = n1;
-              nd_w<P>(v, nb + leaf) = w1;
-            } else {
-              nd_c<P>(v, nb + leaf) = blk;
-              nd_n<P>(v, nb + leaf) += 1;
-              nd_w<P>(v, nb + leaf) += val;
-            }
+            nd_c<P>(v, nb + leaf) = blk;
+            nd_n<P>(v, nb + leaf) += 1;
+            nd_w<P>(v, nb + leaf) += val;
           }
-          unc |= cl == kUncached;
+          unc = 1;
         }
-        if (group_or<P>(unc)) bc.dirty = true;
+        if (group_or<P>(unc)) sf.dirty = true;
       }
       if (lane == 0) {
         v.used[tree] = blk + 1;
@@ -2049,14 +1846,11 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
           R.cw += val;
         }
       }
-      if (refill && fill_slot_vl<G, S>(v, tree, j, limit, started, R, rng, terr, pl, noise, nz, sc, bc) == SIM_ERROR)
+      if (refill && fill_slot_vl<G>(v, tree, j, limit, started, R, rng, terr, pl, noise, nz, sc, sf) == SIM_ERROR)
         break;  // sticky SPMCTS_ERR_STATE; counters flushed below
     }
   }
   if (lane == 0) {
-#ifdef SPMCTS_TREE_PROF
-    sc.prof_flush(8);
-#endif
     sc.flush(v.cnt + (size_t)tree * C_NCNT);
   }
   if (refill && lane == 0) {
@@ -2064,6 +1858,12 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
     if (terr) set_err(v, SPMCTS_ERR_TAPE);
     rng_store(v, tree, rng);
   }
+}
+
+template <class G>
+__global__ __launch_bounds__(64) void k_expand_vl(View v, const float *probs0, const float *values0,
+                                                  const float *probs1, const float *values1) {
+  expand_vl_body<G>(v, probs0, values0, probs1, values1);
 }
 
 // ----------------------------------------------------------------------------
@@ -2576,7 +2376,6 @@ struct spmcts_arena {
   View v;
   std::vector<void *> allocs;
   int n_active;  // active-set size for select / search_end
-  int tree_block;  // threads per workgroup of the threaded tree kernels: 64 (64/P trees per wave) or P (one)
   // cross-lane dedup (spmcts_set_leaf_peer): a follower's leader, a leader's followers, and the events that
   // order the two streams (leader: ev_ins after its table of a step; follower: ev_rows after its rows,
   // ev_push after the leader's outputs reached its rows)
@@ -2598,20 +2397,9 @@ struct spmcts_arena {
 // the same window, one generation apart at most, uses the leader's table -- one table for the GPU's lanes, so a
 // position either lane evaluated serves both -- and inserts only the rows its own network evaluated; otherwise
 // the arena's own table.
-#ifdef SPMCTS_AB
-// SPMCTS_CACHE_SHARE=0 (A/B library): follower lanes keep a table of their own (the first form)
-static bool cache_share_off() {
-  static const bool v = getenv("SPMCTS_CACHE_SHARE") && strcmp(getenv("SPMCTS_CACHE_SHARE"), "0") == 0;
-  return v;
-}
-#else
-static constexpr bool cache_share_off() { return false; }
-#endif
-
 static bool cache_view(const spmcts_arena *h, View &v) {
   v.cshared = 0;
   const spmcts_arena *p = h->peer;
-  if (cache_share_off()) return false;
   if (!v.cwin || !p || p->v.cwin != v.cwin || !p->v.crec) return false;
   const int d = (int)(v.cgen - p->v.cgen);
   if (d < -1 || d > 1) return false;
@@ -2874,27 +2662,6 @@ int spmcts_arena_create(const spmcts_config *cfg, int device, spmcts_arena **out
     delete h;
     return rc;
   }
-#ifndef SPMCTS_AB
-  for (const char *n : {"SPMCTS_TREE_BLOCK", "SPMCTS_EXPAND_CO", "SPMCTS_TREE_COPIES", "SPMCTS_PEER_PUSH",
-                        "SPMCTS_CACHE_SHARE"})
-    if (getenv(n)) {
-      delete h;
-      return fail(SPMCTS_ERR_AB_SWITCH, std::string(n) + " is a switch of the A/B library (make ab: libspmcts_ab.so)");
-    }
-#endif
-  {
-    // Threads per workgroup of the threaded tree kernels (SPMCTS_TREE_BLOCK): P = one tree per wave,
-    // 64 = one wave of 64/P trees, 128..512 = 2..8 such waves.  A tree-kernel wave (~170 VGPRs) leaves no
-    // room on its SIMD for a trunk wave (416 registers), so each tree workgroup keeps a whole CU away from
-    // the other lane's trunk launch while it runs: fewer, fuller workgroups block fewer CUs.
-#ifdef SPMCTS_AB
-    const char *e = getenv("SPMCTS_TREE_BLOCK");  // A/B library only (64 measured best)
-    const int tb = e ? atoi(e) : 64;
-#else
-    const int tb = 64;
-#endif
-    h->tree_block = (tb == h->P || (tb >= 64 && tb <= 512 && tb % 64 == 0)) ? tb : 64;
-  }
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) {
     delete h;
@@ -2971,43 +2738,24 @@ int spmcts_set_leaf_peer(spmcts_arena *h, spmcts_arena *leader) {
   return 0;
 }
 
-#ifdef SPMCTS_AB
-// SPMCTS_PEER_PUSH=leader (A/B library): the push on the leader's own stream ahead of its expand (round 6's
-// first form), instead of on the follower's push stream
-static bool push_on_leader() {
-  static const bool v = getenv("SPMCTS_PEER_PUSH") && strcmp(getenv("SPMCTS_PEER_PUSH"), "leader") == 0;
-  return v;
-}
-#else
-static constexpr bool push_on_leader() { return false; }
-#endif
-
 int spmcts_peer_push(spmcts_arena *h, float *probs_dev, float *values_dev, const float *leader_probs_dev,
                      const float *leader_values_dev, spmcts_stream stream, spmcts_stream leader_stream) {
   if (!h) return fail(-1, "null arena");
   if (!h->peer_step) return 0;
   if (!probs_dev || !values_dev || !leader_probs_dev || !leader_values_dev) return fail(-1, "null argument");
   const hipStream_t s = (hipStream_t)stream, ls = (hipStream_t)leader_stream;
-  if (push_on_leader()) {
-    // on the leader's stream, after its heads of this step (ahead of its expand)
-    HIP_TRY(hipStreamWaitEvent(ls, h->ev_rows, 0));
-    hipLaunchKernelGGL(k_peer_push, dim3(nblk(h->v.NS, 256)), dim3(256), 0, ls, h->v, h->peer->v.srow,
-                       leader_probs_dev, leader_values_dev, probs_dev, values_dev);
-    HIP_TRY(hipEventRecord(h->ev_push, ls));
-  } else {
-    // on the follower's own push stream, once the leader's outputs of this step (everything the caller has
-    // issued on leader_stream: its heads) and our rows are there; the leader's stream goes on at once (its
-    // expand does not wait) and waits for the push only before it next rewrites its table, keys or outputs
-    // (launch_rows: its next step's rows)
-    if (!h->push_stream) HIP_TRY(hipStreamCreateWithFlags(&h->push_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventRecord(h->ev_lead, ls));
-    HIP_TRY(hipStreamWaitEvent(h->push_stream, h->ev_lead, 0));
-    HIP_TRY(hipStreamWaitEvent(h->push_stream, h->ev_rows, 0));
-    hipLaunchKernelGGL(k_peer_push, dim3(nblk(h->v.NS, 256)), dim3(256), 0, h->push_stream, h->v, h->peer->v.srow,
-                       leader_probs_dev, leader_values_dev, probs_dev, values_dev);
-    HIP_TRY(hipEventRecord(h->ev_push, h->push_stream));
-    h->push_pending = true;
-  }
+  // on the follower's own push stream, once the leader's outputs of this step (everything the caller has
+  // issued on leader_stream: its heads) and our rows are there; the leader's stream goes on at once (its
+  // expand does not wait) and waits for the push only before it next rewrites its table, keys or outputs
+  // (launch_rows: its next step's rows)
+  if (!h->push_stream) HIP_TRY(hipStreamCreateWithFlags(&h->push_stream, hipStreamNonBlocking));
+  HIP_TRY(hipEventRecord(h->ev_lead, ls));
+  HIP_TRY(hipStreamWaitEvent(h->push_stream, h->ev_lead, 0));
+  HIP_TRY(hipStreamWaitEvent(h->push_stream, h->ev_rows, 0));
+  hipLaunchKernelGGL(k_peer_push, dim3(nblk(h->v.NS, 256)), dim3(256), 0, h->push_stream, h->v, h->peer->v.srow,
+                     leader_probs_dev, leader_values_dev, probs_dev, values_dev);
+  HIP_TRY(hipEventRecord(h->ev_push, h->push_stream));
+  h->push_pending = true;
   HIP_TRY(hipStreamWaitEvent(s, h->ev_push, 0));
   h->peer_step = false;
   LAUNCH_CHECK();
@@ -3120,26 +2868,6 @@ static int launch_rows(spmcts_arena *h, void *leaves_dev, int32_t *leaf_count_de
   return 0;
 }
 
-#ifdef SPMCTS_AB
-// SPMCTS_TREE_COPIES=1 (A/B library): the threaded tree kernels with 16 LDS block copies per tree
-static bool tree_copies() {
-  static const bool v = getenv("SPMCTS_TREE_COPIES") && strcmp(getenv("SPMCTS_TREE_COPIES"), "1") == 0;
-  return v;
-}
-#endif
-
-#ifdef SPMCTS_TREE_PROF
-// the per-phase cycle sums of the tree kernels since the last reset (g_tprof), into out[16]
-extern "C" int spmcts_ab_tree_prof(unsigned long long *out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tprof), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-  if (reset) {
-    static const unsigned long long zero[16] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_tprof), zero, sizeof(zero)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
-
 int spmcts_select_tree(spmcts_arena *h, spmcts_stream stream) {
   if (!h) return fail(-1, "null arena");
   hipStream_t s = (hipStream_t)stream;
@@ -3147,15 +2875,7 @@ int spmcts_select_tree(spmcts_arena *h, spmcts_stream stream) {
   if (n > 0) {
     const int gpb = 64 / h->P;
     if (h->v.K > 1) {
-      const int tb = h->tree_block, tpb = tb / h->P;
-#ifdef SPMCTS_AB
-      if (tb > 64)
-        DISPATCH(h, hipLaunchKernelGGL((k_select_vl<GG, 512>), dim3(nblk(n, tpb)), dim3(tb), 0, s, h->v, n));
-      else if (tree_copies())
-        DISPATCH(h, hipLaunchKernelGGL((k_select_vl<GG, 64, 16>), dim3(nblk(n, tpb)), dim3(tb), 0, s, h->v, n));
-      else
-#endif
-        DISPATCH(h, hipLaunchKernelGGL(k_select_vl<GG>, dim3(nblk(n, tpb)), dim3(tb), 0, s, h->v, n));
+      DISPATCH(h, hipLaunchKernelGGL(k_select_vl<GG>, dim3(nblk(n, gpb)), dim3(64), 0, s, h->v, n));
     } else {
       DISPATCH(h, hipLaunchKernelGGL(k_select<GG>, dim3(nblk(n, gpb)), dim3(64), 0, s, h->v, n));
     }
@@ -3193,26 +2913,8 @@ int spmcts_expand2(spmcts_arena *h, const float *probs0_dev, const float *values
   }
   const int gpb = 64 / h->P;
   if (h->v.K > 1) {
-    const int tb = h->tree_block, tpb = tb / h->P;
-#ifdef SPMCTS_AB
-    static int co = -1;  // A/B library only: the 96-register co-resident expand (measured slower)
-    if (co < 0) {
-      const char *e = getenv("SPMCTS_EXPAND_CO");
-      co = e && atoi(e) ? 1 : 0;
-    }
-    if (co && tb == 64)
-      DISPATCH(h, hipLaunchKernelGGL(k_expand_vl_co<GG>, dim3(nblk(h->v.T, tpb)), dim3(tb), 0, (hipStream_t)stream,
-                                     h->v, probs0_dev, values0_dev, probs1_dev, values1_dev));
-    else if (tb > 64)
-      DISPATCH(h, hipLaunchKernelGGL((k_expand_vl<GG, 512>), dim3(nblk(h->v.T, tpb)), dim3(tb), 0, (hipStream_t)stream,
-                                     h->v, probs0_dev, values0_dev, probs1_dev, values1_dev));
-    else if (tree_copies())
-      DISPATCH(h, hipLaunchKernelGGL((k_expand_vl<GG, 64, 16>), dim3(nblk(h->v.T, tpb)), dim3(tb), 0, (hipStream_t)stream,
-                                     h->v, probs0_dev, values0_dev, probs1_dev, values1_dev));
-    else
-#endif
-      DISPATCH(h, hipLaunchKernelGGL(k_expand_vl<GG>, dim3(nblk(h->v.T, tpb)), dim3(tb), 0, (hipStream_t)stream, h->v,
-                                     probs0_dev, values0_dev, probs1_dev, values1_dev));
+    DISPATCH(h, hipLaunchKernelGGL(k_expand_vl<GG>, dim3(nblk(h->v.T, gpb)), dim3(64), 0, (hipStream_t)stream, h->v,
+                                   probs0_dev, values0_dev, probs1_dev, values1_dev));
   } else {
     DISPATCH(h, hipLaunchKernelGGL(k_expand<GG>, dim3(nblk(h->v.T, gpb)), dim3(64), 0, (hipStream_t)stream, h->v,
                                    probs0_dev, values0_dev, probs1_dev, values1_dev));

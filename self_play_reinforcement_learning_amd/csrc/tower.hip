@@ -104,8 +104,8 @@ struct Ty<_Float16> {
 };
 
 
-template <int C_, int ROWS_, int W_, int H_, int CG_ = 2, int WAVES_ = 4, int ABL_ = 0, int DEPTH_ = 4, int OCC_ = 1,
-          bool XMAJ_ = false, bool EDGE_ = false, class E_ = __bf16, bool ONEBUF_ = false, bool M16_ = false>
+template <int C_, int ROWS_, int W_, int H_, int CG_ = 2, int WAVES_ = 4, int DEPTH_ = 4, int OCC_ = 1, bool XMAJ_ = false,
+          bool EDGE_ = false, class E_ = __bf16, bool ONEBUF_ = false, bool M16_ = false>
 struct Cfg : Ty<E_> {
   // M16 (tower_m16.h): the block convs on v_mfma_f32_16x16x32 with the phys16 channel order
   static constexpr bool M16 = M16_;
@@ -113,14 +113,6 @@ struct Cfg : Ty<E_> {
   static constexpr int OCC = OCC_;  // resident workgroups per CU the register budget is sized for
   static constexpr int DEPTH = DEPTH_;  // weight-fragment prefetch distance (k-steps)
   static constexpr int C = C_, ROWS = ROWS_, W = W_, H = H_;
-  // ABL: timing ablations for kernel analysis only (results are wrong): 1 = no accumulator init,
-  // 2 = no epilogue store, 4 = no inter-layer barrier, 8 = no LDS operand reads in the k-loop,
-  // 16 = no weight loads in the k-loop, 128 = half the weight loads (m = 0 only).
-  // Schedule/epilogue alternatives (correct results): 64 = accumulator init with bias/residual
-  // (instead of a zero first k-step and bias/residual in the epilogue), 256 = loads issued in a
-  // burst between MFMA blocks (instead of one per MFMA gap), 2048 = packed-math epilogue,
-  // 32768 = weight ring through 64-bit global addresses (instead of a buffer resource).
-  static constexpr int ABL = ABL_;
   static constexpr int WAVES = WAVES_, THREADS = 64 * WAVES_;
   static constexpr int CG = CG_;            // waves split output channels into CG groups ...
   static constexpr int MG = WAVES_ / CG_;   // ... and cell rows into MG groups
@@ -157,7 +149,7 @@ struct Cfg : Ty<E_> {
   // across boards (XMAJ): row = x * (BOARDS * H) + board * H + y, so each board column x of all the
   // tile's boards is BOARDS*H consecutive rows: with 6 boards (36 rows per column) cell tile 0 lies
   // in column 0 and tile 7 in column 6, whose dx = -1 / +1 taps read only zero padding and are
-  // skipped (conv_layer_x): 6 of the 72 (tile, tap) pairs of the workgroup, 8.3 % of the MFMAs.
+  // skipped: 6 of the 72 (tile, tap) pairs of the workgroup, 8.3 % of the MFMAs.
   // A neighbour stays an affine row offset in both layouts: dx * DX + dy.
   static constexpr bool XMAJ = XMAJ_;
   static constexpr int DX = XMAJ ? BOARDS * H : H;
@@ -182,15 +174,6 @@ struct Cfg : Ty<E_> {
     return false;
   }
   __host__ __device__ static constexpr int row_cell(int row) { return row_x(row) * H + row_y(row); }
-  // does any on-board row of 32-row cell tile T have an on-board neighbour column x + dx?
-  __host__ __device__ static constexpr bool tile_dx_live(int T, int dx) {
-    for (int r = T * 32; r < T * 32 + 32 && r < ROWS; ++r) {
-      if (!row_ok(r)) continue;
-      const int nx = row_x(r) + dx;
-      if (nx >= 0 && nx < W) return true;
-    }
-    return false;
-  }
 };
 
 __device__ __forceinline__ bf16x8 lds_b128(const char *p) { return *(const bf16x8 *)p; }
@@ -301,46 +284,8 @@ __device__ __forceinline__ void acc_init(f32x16 (&acc)[K::MT][K::NT], const char
     }
 }
 
-// Epilogue with bias (and residual) added here instead of in the accumulator init (the first
-// k-step's MFMAs then start from zero): out = relu(acc + bias (+ dst)), bf16, into dst.
-template <class K, bool RESID>
-__device__ __forceinline__ void acc_store_bias_relu(const f32x16 (&acc)[K::MT][K::NT], char *dst, const float *bias,
-                                                    int wave, int lane) {
-  static_assert(K::BF16, "timing-ablation epilogue: bf16 tiles only");
-  const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int m = 0; m < K::MT; ++m)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int ch = ((wave % K::CG) * K::MT + m) * 32 + 8 * g + 4 * h;
-      const float4 bv = *(const float4 *)(bias + ch);
-#pragma unroll
-      for (int t = 0; t < K::NT; ++t) {
-        char *p = dst + (((wave / K::CG) * K::NT + t) * 32 + r) * K::RS + phys_off((wave % K::CG) * K::MT + m, h, g);
-        float v0 = acc[m][t][4 * g + 0] + bv.x, v1 = acc[m][t][4 * g + 1] + bv.y;
-        float v2 = acc[m][t][4 * g + 2] + bv.z, v3 = acc[m][t][4 * g + 3] + bv.w;
-        if (RESID) {
-          const bf16x4 x = *(const bf16x4 *)p;
-          v0 += (float)x[0];
-          v1 += (float)x[1];
-          v2 += (float)x[2];
-          v3 += (float)x[3];
-        }
-        bf16x4 o;
-        o[0] = (__bf16)fmaxf(v0, 0.f);
-        o[1] = (__bf16)fmaxf(v1, 0.f);
-        o[2] = (__bf16)fmaxf(v2, 0.f);
-        o[3] = (__bf16)fmaxf(v3, 0.f);
-        *(bf16x4 *)p = o;
-      }
-    }
-}
-
-// ReLU of a pair as bf16: convert, then a signed 16-bit max with 0 (a negative bf16 is a negative int16).
-__device__ __forceinline__ uint32_t relu_pk_bf16(f32x2 v) { return Ty<__bf16>::relu_pk(v); }
-
-// acc_store_bias_relu with the bias already in registers (bv[m][g] = bias[ch(m, g) .. + 4], loaded
-// at the start of the layer so its global-load latency hides under the k-loop instead of stalling
+// Epilogue (the first k-step's MFMAs start from zero; bias and residual are added here): out = relu(acc +
+// bias (+ dst)), into dst, with the bias already in registers (bv[m][g] = bias[ch(m, g) .. + 4], loaded at the start of the layer so its global-load latency hides under the k-loop instead of stalling
 // the epilogue).
 template <class K, bool RESID>
 __device__ __forceinline__ void acc_store_bias_relu_pre(const f32x16 (&acc)[K::MT][K::NT], char *dst,
@@ -389,37 +334,6 @@ __device__ __forceinline__ void acc_store_bias_relu_pre(const f32x16 (&acc)[K::M
   }
 }
 
-// Packed-math form of acc_store_bias_relu: v_pk_add_f32 for bias (and residual), one
-// v_cvt_pk_bf16_f32 per pair, ReLU on the packed bf16 pair as a signed 16-bit max with 0
-// (v_pk_max_i16: a bf16 with the sign bit set is a negative int16).
-
-template <class K, bool RESID>
-__device__ __forceinline__ void acc_store_bias_relu_pk(const f32x16 (&acc)[K::MT][K::NT], char *dst, const float *bias,
-                                                       int wave, int lane) {
-  static_assert(K::BF16, "timing-ablation epilogue: bf16 tiles only");
-  const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int m = 0; m < K::MT; ++m)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int ch = ((wave % K::CG) * K::MT + m) * 32 + 8 * g + 4 * h;
-      const float4 bv = *(const float4 *)(bias + ch);
-      const f32x2 b01 = {bv.x, bv.y}, b23 = {bv.z, bv.w};
-#pragma unroll
-      for (int t = 0; t < K::NT; ++t) {
-        char *p = dst + (((wave / K::CG) * K::NT + t) * 32 + r) * K::RS + phys_off((wave % K::CG) * K::MT + m, h, g);
-        f32x2 lo = f32x2{acc[m][t][4 * g + 0], acc[m][t][4 * g + 1]} + b01;
-        f32x2 hi = f32x2{acc[m][t][4 * g + 2], acc[m][t][4 * g + 3]} + b23;
-        if (RESID) {
-          const uint2 x = *(const uint2 *)p;
-          lo += f32x2{__uint_as_float(x.x << 16), __uint_as_float(x.x & 0xffff0000u)};
-          hi += f32x2{__uint_as_float(x.y << 16), __uint_as_float(x.y & 0xffff0000u)};
-        }
-        *(uint2 *)p = make_uint2(relu_pk_bf16(lo), relu_pk_bf16(hi));
-      }
-    }
-}
-
 template <class K>
 __device__ __forceinline__ void acc_store_relu(const f32x16 (&acc)[K::MT][K::NT], char *dst, int wave, int lane) {
   const int r = lane & 31, h = lane >> 5;
@@ -441,7 +355,6 @@ __device__ __forceinline__ void acc_store_relu(const f32x16 (&acc)[K::MT][K::NT]
 // Software pipeline: the NT B (activation) fragments of step s+1 are read from LDS while the
 // MFMAs of step s run; the A (weight) fragment ring runs DEPTH steps ahead and continues into
 // the next layer's weights (wn_off), so a layer starts with its first weights already in registers.
-// (The A/B library's timing-ablation copy: tower_abl.h conv_layer_abl.)
 template <class K, int KK, int DEPTH, bool RESID>
 __device__ __forceinline__ void conv_layer(const char *src, char *dst, const Nbr<K> &nb, bf16x8 (&a)[DEPTH][K::MT],
                                            const float *bias, int wave, int lane, const WBuf &wb, uint32_t wl_off,
@@ -535,21 +448,11 @@ __device__ __forceinline__ void conv_layer(const char *src, char *dst, const Nbr
 // Per-tap live cell tiles of a column-major / edge-tile layer (Cfg::XMAJ, Cfg::EDGE) for the waves of row
 // group MG_: a tile all of whose rows lie in board column 0 (dx = -1) or W-1 (dx = +1), or whose taps read
 // zero padding only (edge tiles), would multiply zeros; its MFMAs and operand reads are skipped (the
-// skipped contributions are exact zeros).  Used by the 16x16x32 trunk (tower_m16.h) and the A/B library's
-// 32x32x16 k-loops (tower_abl.h).
+// skipped contributions are exact zeros).  Used by the 16x16x32 trunks (tower_m16.h, tower_wide16.h).
 template <class K, int MG_>
 struct XLive {
-  static constexpr uint32_t mask(int g) {
-    uint32_t m = 0;
-    for (int t = 0; t < K::NT; ++t)
-      if (K::tile_dx_live(MG_ * K::NT + t, g - 1)) m |= 1u << t;
-    return m;
-  }
   static constexpr uint32_t popc(uint32_t m) { return m ? (m & 1u) + popc(m >> 1) : 0u; }
   static constexpr uint32_t ALL = (1u << K::NT) - 1;
-  static constexpr uint32_t LIVE[3] = {mask(0), mask(1), mask(2)};
-  // tiles not live in group 0 miss the zero-start step 0: their accumulators start at zero
-  static constexpr uint32_t ZPRE = ALL & ~LIVE[0];
   // per-tap live tiles (Cfg::EDGE: a tile can be dead for taps of one dy as well)
   static constexpr uint32_t lt(int tap) {
     uint32_t m = 0;
@@ -655,9 +558,6 @@ __device__ __forceinline__ void head_layer(const char *src, const bf16x8 *w, con
 // lane l of fragment (ct, tap, kk) holds W[ct*32 + (l & 31)][tap][kk*16 + 8*(l >> 5) + j], j = 0..7.
 // bias: stem C, blocks 2*C each, head C/2.
 // One workgroup's tile: boards [board0, board0 + BOARDS) of the batch (board < batch), all layers.
-#ifdef SPMCTS_AB
-#include "tower_abl.h"  // timing ablations and the 32x32x16 column-group k-loops (A/B library only)
-#endif
 #include "tower_wide.h"
 #include "tower_m16.h"
 #include "tower_wide16.h"
@@ -665,15 +565,9 @@ __device__ __forceinline__ void head_layer(const char *src, const bf16x8 *w, con
 template <class K>
 __device__ __forceinline__ void tower_tile(char *smem, const __bf16 *planes, int batch, int board0, int n_blocks,
                                            const bf16x8 *wpk, const float *bias, uint16_t *out, uint4 *scr) {
-  if constexpr (K::ONEBUF && K::M16) {
+  if constexpr (K::ONEBUF) {
+    static_assert(K::M16, "the one-buffer trunk is the 16x16x32 form (tower_wide16.h)");
     wide16::tile<K>(smem, planes, batch, board0, n_blocks, wpk, bias, out, scr + blockIdx.x * (wide::Scr<K>::PER_WG / 16));
-    return;
-  } else if constexpr (K::ONEBUF) {
-#ifdef SPMCTS_AB
-    wide::tile<K>(smem, planes, batch, board0, n_blocks, wpk, bias, out, scr + blockIdx.x * (wide::Scr<K>::PER_WG / 16));
-#else
-    static_assert(K::M16, "the product's one-buffer trunk is the 16x16x32 form (tower_wide16.h)");
-#endif
     return;
   }
   if constexpr (K::M16 && !K::ONEBUF) {
@@ -740,24 +634,8 @@ __device__ __forceinline__ void tower_tile(char *smem, const __bf16 *planes, int
     const uint32_t wl_off = ct0_off + (uint32_t)((size_t)L * LAYER * 16u);
     const uint32_t wn_off = (kRingAlways && L + 1 == n_convs) ? wl_off : wl_off + (uint32_t)(LAYER * 16u);
     const int wn_steps = L + 1 < n_convs ? LSTEPS : 0;
-#ifdef SPMCTS_AB
-    if constexpr (K::XMAJ || K::ABL != 0) {  // the A/B library's 32x32x16 column-group trunks and ablations
-      const bf16x8 *wl[K::MT], *wn[K::MT];
-#pragma unroll
-      for (int m = 0; m < K::MT; ++m) {
-        const size_t ct = (size_t)((wave % K::CG) * K::MT + m) * LSTEPS * 64 + lane;
-        wl[m] = wblk + (size_t)L * LAYER + ct;
-        wn[m] = wblk + (size_t)(L + 1) * LAYER + ct;
-      }
-      conv_layer_ab<K, KK, DEPTH>(L, X, Y, nb, wl, wn, wn_steps, ring, b, wave, lane, wb, wl_off, wn_off);
-      b += K::C;
-      layer_barrier<K>();
-      continue;
-    }
-#else
-    static_assert(K::M16 || K::ONEBUF || (!K::XMAJ && K::ABL == 0),
-                  "the product's board-major trunk (its column-group tiles: tower_m16.h, tower_wide16.h)");
-#endif
+    static_assert(K::M16 || K::ONEBUF || !K::XMAJ,
+                  "the 32x32x16 trunk is board-major (the column-group tiles: tower_m16.h, tower_wide16.h)");
     if ((L & 1) == 0) {
       conv_layer<K, KK, DEPTH, false>(X, Y, nb, ring, b, wave, lane, wb, wl_off, wn_off, wn_steps);
     } else {
@@ -769,10 +647,6 @@ __device__ __forceinline__ void tower_tile(char *smem, const __bf16 *planes, int
   const bf16x8 *w = wblk + (size_t)n_convs * LAYER;
   head_layer<K>(X, w, b, out, board0, batch, wave, lane);
 }
-
-#ifdef SPMCTS_AB
-#include "tower_ring.h"  // the LDS weight-ring trunk (measured 3-6 % slower; A/B library only)
-#endif
 
 template <class K>
 __global__ __launch_bounds__(K::THREADS) __attribute__((amdgpu_waves_per_eu(K::WAVES / 4 * K::OCC, K::WAVES / 4 * K::OCC))) void k_tower(
@@ -1243,26 +1117,14 @@ static int launch_dyn(const void *planes, const int32_t *count, int max_batch, i
 
 namespace tower {
 #ifdef SPMCTS_AB
-// A/B library (make ab: libspmcts_ab.so, -DSPMCTS_AB) only: switches that select measured-slower
-// alternates and timing ablations.  Read once.
+// A/B library (make ab: libspmcts_ab.so, -DSPMCTS_AB) only: the two alternates a test uses as the reference
+// of a product kernel.  Read once.
 static bool env_is(const char *name, const char *val) {
   const char *e = getenv(name);
   return e && strcmp(e, val) == 0;
 }
-static bool c256_board3() {  // SPMCTS_TOWER_C256=3: the C = 256 trunk on 3-board two-buffer tiles
+static bool c256_board3() {  // SPMCTS_TOWER_C256=3: the C = 256 trunk on 3-board two-buffer tiles (32x32x16 layout)
   static const bool v = env_is("SPMCTS_TOWER_C256", "3");
-  return v;
-}
-static bool wide_tails3() {  // SPMCTS_WIDE_TAILS=3: C = 256 launches with 3-board tail code
-  static const bool v = env_is("SPMCTS_WIDE_TAILS", "3");
-  return v;
-}
-// the C = 256 Connect4 trunk on the 16x16x32 one-buffer tiles (tower_wide16.h, its M16 weight layout) unless
-// SPMCTS_TOWER_C256 (=32: round 4's 32x32x16 one-buffer tiles; =3: the 3-board tiles), SPMCTS_WIDE_TAILS or a
-// SPMCTS_TOWER_CG probe code other than 25xx (all on the 32x32x16 layout) selects another set
-static bool c256_m16() {  // (SPMCTS_TOWER_CG codes 25xx are variants of the 16x16x32 C = 256 trunk)
-  static const bool cg25 = getenv("SPMCTS_TOWER_CG") && atoi(getenv("SPMCTS_TOWER_CG")) / 100 == 25;
-  static const bool v = !getenv("SPMCTS_TOWER_C256") && !getenv("SPMCTS_WIDE_TAILS") && (!getenv("SPMCTS_TOWER_CG") || cg25);
   return v;
 }
 static bool heads_co256() {  // SPMCTS_HEADS_C256=lds: the LDS-staged C = 256 linear heads
@@ -1273,22 +1135,10 @@ static bool heads_co() {  // SPMCTS_HEADS=lds: the LDS-staged linear heads
   static const bool v = !env_is("SPMCTS_HEADS", "lds");
   return v;
 }
-// SPMCTS_TOWER_M16=0: the 32x32x16 C = 128 Connect4 trunk (round 3's kernel set, its weight layout); the
-// ring trunk and the SPMCTS_TOWER_CG variants take that layout too
-static bool m16_trunk() {
-  // SPMCTS_TOWER_CG codes 16xx are variants of the 16x16x32 trunk (its weight layout)
-  static const bool cg16 = getenv("SPMCTS_TOWER_CG") && atoi(getenv("SPMCTS_TOWER_CG")) / 100 == 16;
-  static const bool v =
-      !env_is("SPMCTS_TOWER_M16", "0") && !getenv("SPMCTS_TOWER_RING") && (!getenv("SPMCTS_TOWER_CG") || cg16);
-  return v;
-}
 #else
 // The product library has exactly one kernel per (shape, dtype) and reads no switch; a switch of the
 // A/B library set in the environment is refused (SPMCTS_ERR_AB_SWITCH) rather than silently ignored.
-static constexpr bool m16_trunk() { return true; }
 static constexpr bool c256_board3() { return false; }
-static constexpr bool c256_m16() { return true; }
-static constexpr bool wide_tails3() { return false; }
 static constexpr bool heads_co256() { return true; }
 static constexpr bool heads_co() { return true; }
 #endif
@@ -1298,9 +1148,7 @@ static int ab_switch_guard() {
   return 0;
 #else
   static const int rc = [] {
-    for (const char *n : {"SPMCTS_TOWER_CG", "SPMCTS_TOWER_RING", "SPMCTS_TOWER_C256", "SPMCTS_WIDE_TAILS", "SPMCTS_HEADS",
-                          "SPMCTS_HEADS_C256", "SPMCTS_TREE_BLOCK", "SPMCTS_EXPAND_CO", "SPMCTS_TOWER_M16",
-                          "SPMCTS_TREE_COPIES"})
+    for (const char *n : {"SPMCTS_TOWER_C256", "SPMCTS_HEADS", "SPMCTS_HEADS_C256"})
       if (getenv(n)) return SPMCTS_ERR_AB_SWITCH;
     return 0;
   }();
@@ -1314,44 +1162,29 @@ static int forward_dev(int32_t width, int32_t height, int32_t channels, int32_t 
                        const int32_t *count_dev, int32_t max_batch, const void *weights_dev, const float *bias_dev,
                        void *features_dev, bool pack, hipStream_t s) {
   if (width == 7 && height == 6 && channels == 128) {
-#ifdef SPMCTS_AB
-    if (!m16_trunk())  // round 3's 32x32x16 set: 6-board edge tiles + 4- / 3-board board-major tails
-      return launch_dyn<Cfg<128, 256, 7, 6, 2, 4, 0, 4, 1, true, true, E>, Cfg<128, 192, 7, 6, 2, 4, 0, 4, 1, false, false, E>,
-                        Cfg<128, 128, 7, 6, 2, 4, 0, 4, 1, false, false, E>>(planes_dev, count_dev, max_batch, n_blocks,
-                                                                            weights_dev, bias_dev, features_dev, pack, s);
-#endif
     // 16x16x32 edge tiles for every board, tails included (tower_m16.h)
-    using KM = Cfg<128, 256, 7, 6, 2, 4, 0, 2, 1, true, true, E, false, true>;
+    using KM = Cfg<128, 256, 7, 6, 2, 4, 2, 1, true, true, E, false, true>;
     return launch_dyn<KM, KM, KM>(planes_dev, count_dev, max_batch, n_blocks, weights_dev, bias_dev, features_dev, pack, s);
   }
   if (width == 7 && height == 6 && channels == 256) {
-    // 6-board one-buffer edge tiles (tower_wide.h) with 3-board tails
-    using K3 = Cfg<256, 128, 7, 6, 4, 4, 0, 4, 1, false, false, E>;
-    using KW = Cfg<256, 256, 7, 6, 4, 4, 0, 2, 1, true, true, E, true>;
 #ifdef SPMCTS_AB
+    using K3 = Cfg<256, 128, 7, 6, 4, 4, 4, 1, false, false, E>;
     if (c256_board3())
       return launch_dyn<K3, K3, K3>(planes_dev, count_dev, max_batch, n_blocks, weights_dev, bias_dev, features_dev, pack, s);
-    if (wide_tails3())  // SPMCTS_WIDE_TAILS=3: the round-3 set, 3-board tail tiles in one kernel with the 6-board body
-      return launch_dyn<KW, K3, K3>(planes_dev, count_dev, max_batch, n_blocks, weights_dev, bias_dev, features_dev, pack,
-                                    s);
-    if (!c256_m16())  // SPMCTS_TOWER_C256=32: round 4's 32x32x16 one-buffer tiles for every board
-      return launch_dyn<KW, KW, KW>(planes_dev, count_dev, max_batch, n_blocks, weights_dev, bias_dev, features_dev, pack, s);
 #endif
     // every tile a 6-board one-buffer 16x16x32 tile (tower_wide16.h; a batch tail takes one partly empty tile),
     // so every board goes through the same arithmetic
-    (void)sizeof(K3);
-    (void)sizeof(KW);
-    using KW16 = Cfg<256, 256, 7, 6, 4, 4, 0, 2, 1, true, true, E, true, true>;
+    using KW16 = Cfg<256, 256, 7, 6, 4, 4, 2, 1, true, true, E, true, true>;
     return launch_dyn<KW16, KW16, KW16>(planes_dev, count_dev, max_batch, n_blocks, weights_dev, bias_dev, features_dev,
                                         pack, s);
   }
   if (width == 3 && height == 3 && channels == 128)
-    return launch_dyn<Cfg<128, 256, 3, 3, 2, 4, 0, 4, 1, false, false, E>, Cfg<128, 192, 3, 3, 2, 4, 0, 4, 1, false, false, E>,
-                      Cfg<128, 128, 3, 3, 2, 4, 0, 4, 1, false, false, E>>(planes_dev, count_dev, max_batch, n_blocks,
+    return launch_dyn<Cfg<128, 256, 3, 3, 2, 4, 4, 1, false, false, E>, Cfg<128, 192, 3, 3, 2, 4, 4, 1, false, false, E>,
+                      Cfg<128, 128, 3, 3, 2, 4, 4, 1, false, false, E>>(planes_dev, count_dev, max_batch, n_blocks,
                                                                           weights_dev, bias_dev, features_dev, pack, s);
   if (width == 3 && height == 3 && channels == 256)
-    return launch_dyn<Cfg<256, 128, 3, 3, 4, 4, 0, 4, 1, false, false, E>, Cfg<256, 128, 3, 3, 4, 4, 0, 4, 1, false, false, E>,
-                      Cfg<256, 128, 3, 3, 4, 4, 0, 4, 1, false, false, E>>(planes_dev, count_dev, max_batch, n_blocks,
+    return launch_dyn<Cfg<256, 128, 3, 3, 4, 4, 4, 1, false, false, E>, Cfg<256, 128, 3, 3, 4, 4, 4, 1, false, false, E>,
+                      Cfg<256, 128, 3, 3, 4, 4, 4, 1, false, false, E>>(planes_dev, count_dev, max_batch, n_blocks,
                                                                           weights_dev, bias_dev, features_dev, pack, s);
   return -2;
 }
@@ -1361,147 +1194,24 @@ template <class E>
 static int forward_host(int32_t width, int32_t height, int32_t channels, int32_t n_blocks, const char *pl, int32_t batch,
                         const void *weights_dev, const float *bias_dev, char *ft, hipStream_t s) {
   if (width == 7 && height == 6 && channels == 128) {
-#ifdef SPMCTS_AB
-    if (!m16_trunk())
-      return launch_split<Cfg<128, 256, 7, 6, 2, 4, 0, 4, 1, true, true, E>, Cfg<128, 192, 7, 6, 2, 4, 0, 4, 1, false, false, E>,
-                          Cfg<128, 128, 7, 6, 2, 4, 0, 4, 1, false, false, E>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-#endif
-    using KM = Cfg<128, 256, 7, 6, 2, 4, 0, 2, 1, true, true, E, false, true>;
+    using KM = Cfg<128, 256, 7, 6, 2, 4, 2, 1, true, true, E, false, true>;
     return launch<KM>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
   }
   if (width == 7 && height == 6 && channels == 256) {
-    using K3 = Cfg<256, 128, 7, 6, 4, 4, 0, 4, 1, false, false, E>;
 #ifdef SPMCTS_AB
+    using K3 = Cfg<256, 128, 7, 6, 4, 4, 4, 1, false, false, E>;
     if (c256_board3()) return launch<K3>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-    if (!c256_m16())  // the 32x32x16 one-buffer tiles with 3-board tails (round 4's host path)
-      return launch_split<Cfg<256, 256, 7, 6, 4, 4, 0, 2, 1, true, true, E, true>, K3, K3>(pl, batch, n_blocks,
-                                                                                         weights_dev, bias_dev, ft, s);
 #endif
-    (void)sizeof(K3);
-    return launch<Cfg<256, 256, 7, 6, 4, 4, 0, 2, 1, true, true, E, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev,
+    return launch<Cfg<256, 256, 7, 6, 4, 4, 2, 1, true, true, E, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev,
                                                                                  ft, s);
   }
   if (width == 3 && height == 3 && channels == 128)
-    return launch<Cfg<128, 256, 3, 3, 2, 4, 0, 4, 1, false, false, E>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
+    return launch<Cfg<128, 256, 3, 3, 2, 4, 4, 1, false, false, E>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
   if (width == 3 && height == 3 && channels == 256)
-    return launch<Cfg<256, 128, 3, 3, 4, 4, 0, 4, 1, false, false, E>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
+    return launch<Cfg<256, 128, 3, 3, 4, 4, 4, 1, false, false, E>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
   return -2;
 }
 }  // namespace tower
-
-#ifdef SPMCTS_AB
-namespace tower {
-// Ring trunk launch (tower_ring.h): full 6-board tiles only, for the C = 128 Connect4 net with at most
-// ring::MAX_CONVS / 2 blocks.  count == nullptr: the batch is max_batch.
-template <class E>
-static int launch_ring(const void *planes, const int32_t *count, int max_batch, int n_blocks, const void *w,
-                       const float *b, void *out, hipStream_t s) {
-  using K = Cfg<128, 256, 7, 6, 2, 4, 0, 4, 1, true, true, E>;
-  if (2 * n_blocks > ring::MAX_CONVS) return -2;
-  const int grid = (max_batch + K::BOARDS - 1) / K::BOARDS;
-  if (grid <= 0) return 0;
-  const int lds = ring::Geo<K>::lds(2 * n_blocks);
-  static int attr = 0;
-  if (lds > attr) {
-    if (hipFuncSetAttribute((const void *)ring::k_tower_ring<K>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-        hipSuccess)
-      return -10;
-    attr = lds;
-  }
-  hipLaunchKernelGGL(ring::k_tower_ring<K>, dim3(grid), dim3(256), lds, s, (const __bf16 *)planes, count, max_batch,
-                     n_blocks, (const bf16x8 *)w, b, (uint16_t *)out);
-  return hipGetLastError() == hipSuccess ? 0 : -11;
-}
-
-// SPMCTS_TOWER_RING=1 runs the ring trunk for the C = 128 Connect4 net instead of the two-buffer trunk
-// (measured 3-6 % slower, DESIGN.md §4 "Round 3")
-static bool ring_enabled(int n_blocks) {
-  static const bool on = getenv("SPMCTS_TOWER_RING") && atoi(getenv("SPMCTS_TOWER_RING")) != 0;
-  return on && 2 * n_blocks <= ring::MAX_CONVS;
-}
-
-// SPMCTS_TOWER_CG=<code>: timing alternatives and ablations of the C = 128 trunk (bf16; some give wrong
-// results by design: DESIGN.md §4 has the measurements).  Returns 1 when no code is set.
-static int forward_ab(int32_t width, int32_t height, int32_t channels, int32_t n_blocks, const char *pl, int32_t batch,
-                      const void *weights_dev, const float *bias_dev, char *ft, hipStream_t s) {
-  static const int cg = getenv("SPMCTS_TOWER_CG") ? atoi(getenv("SPMCTS_TOWER_CG")) : -1;
-  if (cg < 0) return 1;
-  if (width == 7 && height == 6 && channels == 128) {
-    switch (cg) {
-#define ABLATE(X) \
-      case 100 + X: return launch<Cfg<128, 256, 7, 6, 2, 4, X>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      ABLATE(0) ABLATE(1) ABLATE(2) ABLATE(4) ABLATE(8) ABLATE(16) ABLATE(24) ABLATE(31) ABLATE(64) ABLATE(128)
-      ABLATE(256) ABLATE(2048) ABLATE(32768)
-#undef ABLATE
-#define ABLATE_EDGE(X) \
-      case 200 + X: return launch<Cfg<128, 256, 7, 6, 2, 4, X, 4, 1, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      ABLATE_EDGE(0) ABLATE_EDGE(2) ABLATE_EDGE(4) ABLATE_EDGE(6) ABLATE_EDGE(8) ABLATE_EDGE(16) ABLATE_EDGE(24)
-      ABLATE_EDGE(30) ABLATE_EDGE(128) ABLATE_EDGE(512)
-      case 301: return launch<Cfg<128, 256, 7, 6, 2, 4, 4096, 4, 1, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      // weight-major MFMA order within a k-step (bit-identical; clock / operand-toggling probe)
-      case 304: return launch<Cfg<128, 256, 7, 6, 2, 4, 4194304, 4, 1, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      // the 16x16x32 trunk (tower_m16.h, the default: DEPTH 2, grouped schedule) variants: weight ring 4 deep
-      // (1604), the compiler's own schedule (1600)
-      case 1604: return launch<Cfg<128, 256, 7, 6, 2, 4, 0, 4, 1, true, true, __bf16, false, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      case 1600: return launch<Cfg<128, 256, 7, 6, 2, 4, 256, 2, 1, true, true, __bf16, false, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      case 1602: return launch<Cfg<128, 256, 7, 6, 2, 4, 0, 2, 1, true, true, __bf16, false, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      // 4 channel quarters x all 8 cell tiles (one weight fragment per 16 MFMAs instead of per 8, twice the LDS
-      // operand reads; the B fragments conflict-free since round 5): ring depth 2 (1640) and 4 (1644)
-      case 1640: return launch<Cfg<128, 256, 7, 6, 4, 4, 0, 2, 1, true, true, __bf16, false, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      case 1644: return launch<Cfg<128, 256, 7, 6, 4, 4, 0, 4, 1, true, true, __bf16, false, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      // timing ablations of the shipped 16x16x32 trunk (wrong results): no weight loads in the k-loop (1616), no
-      // LDS operand reads (1608) -- upper bounds on what fewer weight / operand fetches per MFMA could buy
-      case 1616: return launch<Cfg<128, 256, 7, 6, 2, 4, 16, 2, 1, true, true, __bf16, false, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      case 1608: return launch<Cfg<128, 256, 7, 6, 2, 4, 8, 2, 1, true, true, __bf16, false, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      // timing ablation (wrong results): every layer streams layer 0's weights (an L2-resident set): what the
-      // trunk's fabric re-stream of its 11.8 MB weight set costs
-      case 1665: return launch<Cfg<128, 256, 7, 6, 2, 4, 65536, 2, 1, true, true, __bf16, false, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      // timing ablation (wrong results): two 16x16x32 MFMAs per 32x32x16 (the MFMA-shape clock probe)
-      case 308: return launch<Cfg<128, 256, 7, 6, 2, 4, 8388608, 4, 1, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      case 302: return launch<Cfg<128, 256, 7, 6, 2, 4, 8192, 4, 1, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      case 316: return launch<Cfg<128, 256, 7, 6, 2, 4, 16384, 4, 1, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-#undef ABLATE_EDGE
-      // four channel quarters x one row group (each wave all 8 cell tiles, one weight fragment per k-step)
-      case 400: return launch<Cfg<128, 256, 7, 6, 4, 4, 0, 4, 1, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      case 408: return launch<Cfg<128, 256, 7, 6, 4, 4, 0, 8, 1, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      // eight waves (two per SIMD): four channel quarters x two row halves, one weight fragment per k-step
-      case 800: return launch<Cfg<128, 256, 7, 6, 4, 8, 0, 4, 1, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      case 808: return launch<Cfg<128, 256, 7, 6, 4, 8, 0, 8, 1, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-      case 250: return launch<Cfg<128, 256, 7, 6, 2, 4, 0, 8, 1, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);  // ring depth 8
-      case 10: return launch_split<Cfg<128, 256, 7, 6, 2>, Cfg<128, 128, 7, 6, 2>, Cfg<128, 128, 7, 6, 2>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);  // two tile sizes only
-      case 15: return launch_split<Cfg<128, 256, 7, 6, 2, 4, 0, 4, 1, true>, Cfg<128, 192, 7, 6, 2>, Cfg<128, 128, 7, 6, 2>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);  // column-major tiles without edge rows
-      case 11: return launch_split<Cfg<128, 256, 7, 6, 2>, Cfg<128, 192, 7, 6, 2>, Cfg<128, 128, 7, 6, 2>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);  // board-major full tiles
-      default: return 1;
-    }
-  }
-  // the MFMA-shape clock probe on the C = 256 one-buffer trunk (timing only, wrong results: each 32x32x16 as two
-  // 16x16x32 on the same operands, as code 308 for C = 128) and its reference (2300 = the shipped trunk)
-  if (width == 7 && height == 6 && channels == 256 && cg == 2308)
-    return launch_split<Cfg<256, 256, 7, 6, 4, 4, 8388608, 2, 1, true, true, __bf16, true>, Cfg<256, 128, 7, 6, 4>,
-                        Cfg<256, 128, 7, 6, 4>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-  if (width == 7 && height == 6 && channels == 256 && cg == 2300)
-    return launch_split<Cfg<256, 256, 7, 6, 4, 4, 0, 2, 1, true, true, __bf16, true>, Cfg<256, 128, 7, 6, 4>,
-                        Cfg<256, 128, 7, 6, 4>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-  // the 16x16x32 one-buffer C = 256 trunk (tower_wide16.h, the product's) and two variants: a 4-deep weight ring
-  // (2564), the compiler's own k-loop schedule (2556)
-  if (width == 7 && height == 6 && channels == 256 && cg == 2560)
-    return launch<Cfg<256, 256, 7, 6, 4, 4, 0, 2, 1, true, true, __bf16, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-  if (width == 7 && height == 6 && channels == 256 && cg == 2564)
-    return launch<Cfg<256, 256, 7, 6, 4, 4, 0, 4, 1, true, true, __bf16, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-  if (width == 7 && height == 6 && channels == 256 && cg == 2556)
-    return launch<Cfg<256, 256, 7, 6, 4, 4, 256, 2, 1, true, true, __bf16, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-  if (width == 7 && height == 6 && channels == 256 && cg == 254)  // the one-buffer trunk with a 4-deep weight ring
-    return launch_split<Cfg<256, 256, 7, 6, 4, 4, 0, 4, 1, true, true, __bf16, true>, Cfg<256, 128, 7, 6, 4>,
-                        Cfg<256, 128, 7, 6, 4>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-  // the round-3 residual-scratch pointer form (64-bit nontemporal accesses, 110 spills) against the shipped
-  // buffer-resource form (tower_wide.h ScrBuf)
-  if (width == 7 && height == 6 && channels == 256 && cg == 2566)
-    return launch_split<Cfg<256, 256, 7, 6, 4, 4, 2097152, 2, 1, true, true, __bf16, true>, Cfg<256, 128, 7, 6, 4>,
-                        Cfg<256, 128, 7, 6, 4>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-  return 1;
-}
-}  // namespace tower
-#endif  // SPMCTS_AB
 
 extern "C" int spmcts_tower_forward_dev(int32_t width, int32_t height, int32_t channels, int32_t n_blocks,
                                         const void *planes_dev, const int32_t *count_dev, int32_t max_batch,
@@ -1513,11 +1223,6 @@ extern "C" int spmcts_tower_forward_dev(int32_t width, int32_t height, int32_t c
   if (const int g = ab_switch_guard()) return g;
   if (max_batch == 0) return 0;
   const bool pack = (flags & SPMCTS_TOWER_PACK) != 0;
-#ifdef SPMCTS_AB
-  if (width == 7 && height == 6 && channels == 128 && ring_enabled(n_blocks))
-    return (flags & SPMCTS_TOWER_F16 ? launch_ring<_Float16> : launch_ring<__bf16>)(
-        planes_dev, count_dev, max_batch, n_blocks, weights_dev, bias_dev, features_dev, s);
-#endif
   if (flags & SPMCTS_TOWER_F16)
     return forward_dev<_Float16>(width, height, channels, n_blocks, planes_dev, count_dev, max_batch, weights_dev,
                                  bias_dev, features_dev, pack, s);
@@ -1534,16 +1239,6 @@ extern "C" int spmcts_tower_forward(int32_t width, int32_t height, int32_t chann
   if (const int g = ab_switch_guard()) return g;
   const char *pl = (const char *)planes_dev;
   char *ft = (char *)features_dev;
-#ifdef SPMCTS_AB
-  // the ring trunk serves both element types on both paths (as spmcts_tower_forward_dev)
-  if (width == 7 && height == 6 && channels == 128 && ring_enabled(n_blocks) && !getenv("SPMCTS_TOWER_CG"))
-    return (flags & SPMCTS_TOWER_F16 ? launch_ring<_Float16> : launch_ring<__bf16>)(
-        planes_dev, nullptr, batch, n_blocks, weights_dev, bias_dev, features_dev, s);
-  if (!(flags & SPMCTS_TOWER_F16)) {
-    const int rc = forward_ab(width, height, channels, n_blocks, pl, batch, weights_dev, bias_dev, ft, s);
-    if (rc != 1) return rc;
-  }
-#endif
   if (flags & SPMCTS_TOWER_F16)
     return forward_host<_Float16>(width, height, channels, n_blocks, pl, batch, weights_dev, bias_dev, ft, s);
   return forward_host<__bf16>(width, height, channels, n_blocks, pl, batch, weights_dev, bias_dev, ft, s);
@@ -1642,7 +1337,7 @@ extern "C" int spmcts_tower_supported(int32_t width, int32_t height, int32_t cha
 extern "C" int spmcts_tower_weight_layout(int32_t width, int32_t height, int32_t channels) {
   using namespace tower;
   if (!spmcts_tower_supported(width, height, channels)) return -2;
-  if (width == 7 && height == 6 && channels == 128 && m16_trunk()) return SPMCTS_WLAYOUT_M16;
-  if (width == 7 && height == 6 && channels == 256 && c256_m16()) return SPMCTS_WLAYOUT_M16;
+  if (width == 7 && height == 6 && channels == 128) return SPMCTS_WLAYOUT_M16;
+  if (width == 7 && height == 6 && channels == 256 && !c256_board3()) return SPMCTS_WLAYOUT_M16;
   return SPMCTS_WLAYOUT_32X32;
 }

@@ -23,8 +23,8 @@
 
 namespace m16 {
 
-// 16-channel output tiles per wave: 4 with the 2 x 2 wave plan (channel halves x row halves, the product
-// trunk), 2 with 4 x 1 (channel quarters x all rows, A/B code 1640)
+// 16-channel output tiles per wave: 4 with the C = 128 trunk's 2 x 2 wave plan (channel halves x row halves) and
+// with the C = 256 trunk's 4 x 1 (channel quarters x all rows, tower_wide16.h)
 template <class K>
 constexpr int MM = K::C / 16 / K::CG;
 
@@ -160,25 +160,6 @@ __device__ __forceinline__ void conv_tap(const char *src, const Nbr<K> &nb, f32x
   }
 }
 
-#ifdef SPMCTS_AB
-#include "tower_m16_abl.h"  // the k-loop's timing ablations (A/B library only)
-#endif
-
-// a tap of conv_layer: the product's conv_tap (or, in the A/B library, the ablation copy for a Cfg::ABL code)
-template <class K, int KK32, int DEPTH, int MG_, int TAP>
-__device__ __forceinline__ void tap(const char *src, const Nbr<K> &nb, f32x4 (&acc)[MM<K>][K::NT][2],
-                                    bf16x8 (&bc)[K::NT][2], bf16x8 (&bn)[K::NT][2], int (&off_cur)[K::NT][2],
-                                    int (&off_nxt)[K::NT][2], bf16x8 (&a)[DEPTH][MM<K>], int qoff, int rb,
-                                    const WBuf &wb, uint32_t wl_off, uint32_t wn_off, int wn_steps) {
-#ifdef SPMCTS_AB
-  if constexpr (K::ABL != 0) {
-    conv_tap_abl<K, KK32, DEPTH, MG_, TAP>(src, nb, acc, bc, bn, off_cur, off_nxt, a, qoff, rb, wb, wl_off, wn_off, wn_steps);
-    return;
-  }
-#endif
-  conv_tap<K, KK32, DEPTH, MG_, TAP>(src, nb, acc, bc, bn, off_cur, off_nxt, a, qoff, rb, wb, wl_off, wn_off, wn_steps);
-}
-
 // out = relu(acc + bias (+ the block input at the same physical positions, RESID)), into dst.
 template <class K, bool RESID>
 __device__ __forceinline__ void epilogue(const f32x4 (&acc)[MM<K>][K::NT][2], char *dst, const float4 (&bv)[MM<K>],
@@ -250,7 +231,7 @@ __device__ __forceinline__ void conv_layer(const char *src, char *dst, const Nbr
         bc[t][h] = lds_b128(src + off_cur[t][h]);
       }
     }
-#define TAP16(T) tap<K, KK32, DEPTH, MG_, T>(src, nb, acc, bc, bn, off_cur, off_nxt, a, qoff, rb, wb, wl_off, wn_off, wn_steps)
+#define TAP16(T) conv_tap<K, KK32, DEPTH, MG_, T>(src, nb, acc, bc, bn, off_cur, off_nxt, a, qoff, rb, wb, wl_off, wn_off, wn_steps)
   TAP16(0); TAP16(1); TAP16(2); TAP16(3); TAP16(4); TAP16(5); TAP16(6); TAP16(7); TAP16(8);
 #undef TAP16
   epilogue<K, RESID>(acc, dst, bv, cg, MG_, q, rb);
@@ -362,16 +343,8 @@ __device__ __forceinline__ void tile(char *smem, const __bf16 *planes, int batch
   const int cg_u = __builtin_amdgcn_readfirstlane(cg);
   const uint32_t ct0_off = (uint32_t)(STEM + (size_t)(NM * cg_u) * LSTEPS * 64) * 16u;
   for (int L = 0; L < n_convs; ++L) {
-#ifdef SPMCTS_AB
-    // timing ablation (A/B code 1665, wrong results): every layer streams layer 0's weights, an L2-resident
-    // 295 KB set instead of 11.8 MB re-streamed from the fabric per round of workgroups
-    const bool l2w = (K::ABL & 65536) != 0;
-    const uint32_t wl_off = ct0_off + (l2w ? 0u : (uint32_t)((size_t)L * LAYER * 16u));
-    const uint32_t wn_off = (l2w || (kRingAlways && L + 1 == n_convs)) ? wl_off : wl_off + (uint32_t)(LAYER * 16u);
-#else
     const uint32_t wl_off = ct0_off + (uint32_t)((size_t)L * LAYER * 16u);
     const uint32_t wn_off = (kRingAlways && L + 1 == n_convs) ? wl_off : wl_off + (uint32_t)(LAYER * 16u);
-#endif
     const int wn_steps = L + 1 < n_convs ? LSTEPS : 0;
     const bool even = (L & 1) == 0;
     if (K::MG == 1 || wave / K::CG == 0) {

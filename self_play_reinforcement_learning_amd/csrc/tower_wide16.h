@@ -8,8 +8,8 @@
 //   * per wave: 4 16-channel tiles (64 output channels: one whole phys16 group, so a lane's 16 outputs of
 //     a cell are one contiguous 32-byte run) x 8 cell tiles x 2 row fragments = 64 f32x4 accumulators
 //     (the full AGPR file, as the 32x32x16 form's 16 f32x16);
-//   * the same FLOPs, LDS bytes and weight bytes per k-step as tower_wide.h; a timing probe on that kernel
-//     (each 32x32x16 as two 16x16x32 on the same operands, A/B code 2308) ran the trunk 6.5 % faster at
+//   * the same FLOPs, LDS bytes and weight bytes per k-step as the 32x32x16 one-buffer trunk it replaced; a
+//     timing probe on that kernel (each 32x32x16 as two 16x16x32 on the same operands) ran the trunk 6.5 % faster at
 //     a 1.90 vs 1.80 GHz clock (profiles/r05/c256/shape_probe.txt);
 //   * residual scratch per workgroup: [wave][cell tile t][fragment h][64 lanes] x 32 bytes (the lane's run),
 //     the same 128 KB as tower_wide.h's, through the same buffer resource (stores at soffset 0).
@@ -99,7 +99,9 @@ __device__ __forceinline__ void conv(char *X, const Nbr<K> &nb, bf16x8 (&a)[DEPT
   static_assert(K::C == K::THREADS, "one bias value per thread");
   static_assert(KK32 % DEPTH == 0, "ring slot must be a compile-time function of k");
   const int q = lane >> 4, rb = lane_row(lane & 15), qoff = 16 * q;
-  // the epilogue's bias: one value per thread now, staged in LDS after the k-loop (as tower_wide.h)
+  // the epilogue's bias: one value per thread now, staged in LDS after the k-loop (1 register
+  // through the k-loop instead of 32; the previous layer's epilogue finished reading the staging area at its
+  // closing barrier)
   const float bmine = bias[threadIdx.x];
   f32x4 acc[4][K::NT][2];
 #pragma unroll
@@ -130,7 +132,7 @@ __device__ __forceinline__ void conv(char *X, const Nbr<K> &nb, bf16x8 (&a)[DEPT
   epilogue<K, RESID, SAVE>(X, acc, bv, scr, wave, q, rb, lane);
 }
 
-// Stem (3 planes padded to one 16-channel k-step per tap, 32x32x16 as tower_wide.h's, bias in the
+// Stem (3 planes padded to one 16-channel k-step per tap, on 32x32x16 MFMAs, bias in the
 // accumulators), stored in the phys16 order in place; then each lane copies its runs (the first block's
 // input) to scratch in the layout the epilogue reads.
 template <class K>
@@ -234,7 +236,9 @@ __device__ __forceinline__ void tile(char *smem, const __bf16 *planes, int batch
   wb.voff = lane * 16;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const uint32_t ct0_off = (uint32_t)(STEM + (size_t)(4 * wave_u) * LSTEPS * 64) * 16u;
-  // one iteration per residual block (a straight line; see tower_wide.h)
+  // one iteration per residual block: its first conv, then its second (residual + save) -- a straight line,
+  // where an odd/even branch per conv made the register allocator merge the two bodies' live ranges at the
+  // branch (66 spilled VGPRs, reloaded there)
   for (int L = 0; L < n_convs; L += 2) {
     const uint32_t wl_off = ct0_off + (uint32_t)((size_t)L * LAYER * 16u);
     conv<K, DEPTH, false, false>(X, nb, ring, b, wave, lane, wb, wl_off, wl_off + (uint32_t)(LAYER * 16u), LSTEPS, scr,

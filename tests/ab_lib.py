@@ -1,6 +1,8 @@
 """The A/B library (make -C self_play_reinforcement_learning_amd/csrc ab: libspmcts_ab.so, -DSPMCTS_AB) holds
-the measured-slower alternates and timing ablations behind environment switches; the product library refuses
-those switches (SPMCTS_ERR_AB_SWITCH).  GPU tests of an alternate run it in a child process on this library."""
+the two alternates that tests use as the reference of a product kernel -- the LDS-staged heads (SPMCTS_HEADS=lds,
+SPMCTS_HEADS_C256=lds) and the C = 256 trunk on 3-board tiles (SPMCTS_TOWER_C256=3) -- behind environment
+switches; the product library refuses those switches (SPMCTS_ERR_AB_SWITCH).  GPU tests of an alternate run it
+in a child process on this library."""
 import os
 import subprocess
 import sys
@@ -23,10 +25,8 @@ def ab_env(**switches):
 
 def product_env():
     """Environment of a child process on the product library (no A/B switch set)."""
-    env = {k: v for k, v in os.environ.items() if k != "SPMCTS_LIB" and not k.startswith(("SPMCTS_TOWER_", "SPMCTS_HEADS",
-                                                                                            "SPMCTS_WIDE_", "SPMCTS_TREE_BLOCK",
-                                                                                            "SPMCTS_EXPAND_CO", "SPMCTS_TREE_COPIES",
-                                                                                            "SPMCTS_PEER_PUSH"))}
+    env = {k: v for k, v in os.environ.items()
+           if k != "SPMCTS_LIB" and not k.startswith(("SPMCTS_TOWER_", "SPMCTS_HEADS"))}
     return env
 
 

@@ -206,53 +206,6 @@ def test_fp16_bench_nets_finite_and_close(ff):
     assert e_hip <= 2 * e_ac + 2e-3, (e_hip, e_ac)
 
 
-_RING_CHILD = r"""
-import json, sys, torch
-sys.path.insert(0, {repo!r})
-from self_play_reinforcement_learning_amd.evaluator import HipTowerEvaluator
-from tests.test_gpu_tower import _net, _planes
-out = {{}}
-for dt in (torch.bfloat16, torch.float16):
-    net = _net(7, 6, 7, 20, 32)
-    x = _planes(7, 6, 999)
-    with torch.no_grad():
-        rp, rv = net.forward_planes(x)
-    hip = HipTowerEvaluator(net, dtype=dt)
-    xb = x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-    p, v = hip(xb)
-    cnt = torch.tensor([999], dtype=torch.int32, device=x.device)
-    pd, vd = hip.forward_dev(xb, cnt, 999)
-    torch.cuda.synchronize()
-    p7, v7 = hip(xb[:7].contiguous(memory_format=torch.channels_last))
-    out[str(dt)] = dict(err=max((p - rp).abs().max().item(), (v - rv.view(-1)).abs().max().item()),
-                        dev_equal=bool(torch.equal(pd[:999], p) and torch.equal(vd[:999].view(-1), v.view(-1))),
-                        batch_equal=bool(torch.equal(p7, p[:7]) and torch.equal(v7, v[:7])))
-print(json.dumps(out))
-"""
-
-
-def test_ring_trunk_variant():
-    """The LDS weight-ring trunk (csrc/tower_ring.h, SPMCTS_TOWER_RING=1: read once per process, so it
-    runs in a child process): the same tolerance against the fp32 forward as the default trunk
-    (test_tower_matches_fp32_reference's 0.05 bound), bit-identical device-count and host-count
-    outputs, and batch independence.  Measured slower than the default trunk."""
-    import json
-    import os
-    import subprocess
-    import sys
-
-    from tests.ab_lib import ab_env
-
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = ab_env(SPMCTS_TOWER_RING="1")  # the ring trunk is in the A/B library only
-    r = subprocess.run([sys.executable, "-c", _RING_CHILD.format(repo=repo)], env=env, capture_output=True, text=True,
-                       timeout=240, cwd=repo)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    for dt, d in res.items():
-        assert d["err"] < 0.05 and d["dev_equal"] and d["batch_equal"], (dt, d)
-
-
 _WIDE_CHILD = r"""
 import sys, numpy as np, torch
 sys.path.insert(0, sys.argv[1])
@@ -272,13 +225,13 @@ np.savez(sys.argv[2], **out)
 
 
 def test_c256_tile_sets(tmp_path):
-    """The C = 256 trunk's tile sets (each in its own process: the switches are read once):
-    * the A/B library's 6-board one-buffer 32x32x16 tiles (tower_wide.h, round 4's product trunk,
-      SPMCTS_TOWER_C256=32) give every board the same bits as its 3-board tiles (SPMCTS_TOWER_C256=3): host
-      batch (full tiles + tails) and the device-count path on a ragged batch, bf16 and fp16;
-    * the product library's 16x16x32 one-buffer tiles (tower_wide16.h, its own M16 weight blob) agree with
-      them within 1e-2 on probabilities and values (the same products summed in another order; each is
-      checked against the fp32 module by test_tower_matches_fp32_reference)."""
+    """The C = 256 trunk's tile sets (each in its own process: the switch is read once): the product library's
+    6-board one-buffer 16x16x32 tiles (tower_wide16.h, its own M16 weight blob) agree with the A/B library's
+    3-board two-buffer 32x32x16 tiles (SPMCTS_TOWER_C256=3) within 1e-2 on probabilities and values (the same
+    products summed in another order; each is checked against the fp32 module by
+    test_tower_matches_fp32_reference): host batch (full tiles + tails) and the device-count path on a ragged
+    batch, bf16 and fp16.  (The 6-board one-buffer 32x32x16 tiles, which gave the 3-board tiles' bits, were
+    removed: DESIGN.md §4.)"""
     import os
     import subprocess
     import sys
@@ -287,12 +240,10 @@ def test_c256_tile_sets(tmp_path):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = {}
-    for tiles, env in (("3", ab_env(SPMCTS_TOWER_C256="3")), ("32", ab_env(SPMCTS_TOWER_C256="32")),
-                       ("16", product_env())):
+    for tiles, env in (("3", ab_env(SPMCTS_TOWER_C256="3")), ("16", product_env())):
         out = tmp_path / f"c{tiles}.npz"
         subprocess.run([sys.executable, "-c", _WIDE_CHILD, root, str(out)], env=env, check=True, timeout=300)
         res[tiles] = np.load(out)
     for k in res["3"].files:
-        assert np.array_equal(res["3"][k], res["32"][k]), k
-        assert np.abs(res["16"][k].astype(np.float64) - res["32"][k]).max() < 1e-2, k
-        assert not np.array_equal(res["16"][k], res["32"][k]), k  # the product really runs the other kernel
+        assert np.abs(res["16"][k].astype(np.float64) - res["3"][k]).max() < 1e-2, k
+        assert not np.array_equal(res["16"][k], res["3"][k]), k  # the product really runs the other kernel

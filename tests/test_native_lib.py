@@ -143,7 +143,7 @@ def test_product_library_holds_only_the_shipped_trunk_kernels():
     """The product build (make; no -DSPMCTS_AB) has one trunk kernel set per (board shape, channels,
     dtype): 8 k_tower_dyn (device-count path: 7x6 and 3x3, C = 128 and 256, bf16 and fp16; since round 5
     the 7x6 C = 256 set is the 6-board one-buffer 16x16x32 tiles alone, tails included) and 8 k_tower
-    (host-count path tiles, one per shape and dtype), every Cfg without a timing ablation (ABL = 0), the
+    (host-count path tiles, one per shape and dtype), the
     7x6 C = 128 trunk only as the 16x16x32 (M16) two-buffer tiles and the 7x6 C = 256 trunk only as the M16
     one-buffer tiles (tower_wide16.h), the co-resident heads only, and no ring / LDS-heads / ablation kernel."""
     path = _lib.LIB_PATH
@@ -160,9 +160,9 @@ def test_product_library_holds_only_the_shipped_trunk_kernels():
     # the 7x6 C = 256 kernels: Cfg<256, 256, 7, 6, ..., ONEBUF = true, M16 = true> only
     c256 = [n for n in dyn + host if "CfgILi256ELi" in n and "ELi7ELi6E" in n]
     assert len(c256) == 4 and all("CfgILi256ELi256ELi7ELi6E" in n and "Lb1ELb1EE" in n for n in c256), c256
-    # Cfg<C, ROWS, W, H, CG, WAVES, ABL, ...>: the 7th argument is 0 in every instantiation
-    cfgs = re.findall(r"(?:CfgI|NS1_I)Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", " ".join(dyn + host))
-    assert cfgs and all(c[6] == "0" for c in cfgs)
+    # Cfg<C, ROWS, W, H, CG, WAVES, ...>
+    cfgs = re.findall(r"(?:CfgI|NS1_I)Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", " ".join(dyn + host))
+    assert cfgs
     assert {(c[0], c[2], c[3]) for c in cfgs} == {("128", "7", "6"), ("256", "7", "6"), ("128", "3", "3"),
                                                  ("256", "3", "3")}
     assert not [n for n in names if "ring" in n or n.startswith("_ZN5tower7k_headsI")]
@@ -179,9 +179,9 @@ def test_product_library_refuses_ab_switches(monkeypatch):
 
     code = ("import ctypes, sys; sys.path.insert(0, %r); from self_play_reinforcement_learning_amd import _lib; "
             "L = _lib.lib(); print(L.spmcts_tower_forward(7, 6, 128, 20, None, 0, None, None, None, 0, None))" % REPO)
-    env = dict(os.environ, SPMCTS_TOWER_CG="200")
+    env = dict(os.environ, SPMCTS_HEADS="lds")
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True).stdout
     assert out.split()[-1] == "-5"
-    env.pop("SPMCTS_TOWER_CG")
+    env.pop("SPMCTS_HEADS")
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True).stdout
     assert out.split()[-1] == "0"  # batch 0: nothing to do, no GPU call
