@@ -1,0 +1,161 @@
+// arena_view.h — the device view of an arena (View), the node-record accessors, set_err, nbase.
+// Included by spmcts.hip, first of the arena headers: needs board.h and spmcts.h.
+// ----------------------------------------------------------------------------
+// device view of an arena (passed by value to kernels)
+// ----------------------------------------------------------------------------
+typedef rocrand_state_philox4x32_10 Philox;
+
+struct View {
+  int T, cap, G, A;
+  int iters;  // MCTreeSearch.iterations (bounds the last step of a K-in-flight search)
+  int K, NS;  // simulations in flight per tree (virtual loss; 1 = sequential), pending slots = T * K
+  double cpuct, x, alpha;
+  int strong, evaluate, rng_mode, leaf_format, leaf_layout;
+  // node store: one record of 32 * P bytes per child block (nd_* below)
+  char *nodes;
+  // trees
+  int32_t *root;
+  uint64_t *rpos, *rneg;
+  int8_t *rplayer;
+  int32_t *used;
+  int32_t gc;         // 1: blocks_per_tree below the worst case -> compaction before a search (k_compact)
+  int32_t *gc_list;   // [T][cap] scratch: live blocks (BFS order)
+  int32_t *gc_map;    // [T][cap] scratch: old block -> new block (-1 dead)
+  int32_t *tstarted;  // threaded search: search_node calls started in the current search (inactive: >= limit)
+  double *noise;
+  uint8_t *noise_on;
+  int32_t *pnode;   // [T][MAXD] path node ids (root .. parent of leaf)
+  int32_t *pn;      // [T][MAXD] their visit counts as read during select
+  double *pw;       // [T][MAXD] their w as read during select
+  int32_t *plen;
+  int32_t *leaf;    // leaf node (local id)
+  int32_t *leaf_n;
+  double *leaf_w;
+  uint64_t *lpos, *lneg;
+  int8_t *lmover;
+  uint8_t *need;
+  Philox *rng;
+  const double *tape;
+  const int64_t *tape_end;  // [T] end offset
+  int64_t *tape_cur;        // [T]
+  int64_t *cnt;             // per-tree counters [T][8]
+  int32_t *active;
+  int32_t *row_tree;  // row -> pending slot (tree * K + j)
+  int32_t *srow;      // pending slot -> row (K > 1)
+  int32_t *row_count;
+  // batch leaf dedup (K > 1, spmcts_set_leaf_dedup): pending leaves with the same network input share
+  // one row.  dtab: open-addressing table of (generation << 32 | owner slot), dent: a slot's entry
+  uint64_t *dtab;
+  int32_t *dent;
+  uint8_t *down;  // 1 = the slot owns its key's row, 2 = the leader lane's row serves it (set per step)
+  int dedup, dmask;
+  uint32_t dgen;
+  // cross-lane dedup (round 6, spmcts_set_leaf_peer): a leader arena keeps each owner slot's key in okey
+  // (2 x u64 per slot) for the step; a follower's owner slot whose key the leader evaluates this step
+  // takes the leader's row (down 2, xpeer = the leader's owner slot), copied in by k_peer_push
+  uint64_t *okey;
+  int32_t *xpeer;
+  int lead;     // 1: this arena has followers (k_dedup_owner writes okey)
+  int peer_on;  // 1 in a follower's simulation-step launches (k_scan_need numbers down-2 slots after its own rows)
+  // evaluation cache (round 6, spmcts_set_eval_cache): network outputs of the arena's own rows kept for `cwin`
+  // generations (one per ply / search), keyed like the dedup table; an owner slot whose key is there takes
+  // the cached outputs (down 3, xc = the entry) in a row after the network rows, filled by k_cache_io.
+  // crec: one 64-byte record per entry (one line per probe): tag u64 ((generation << 32) | state, 0 = never used),
+  // own u64, opp u64, then A probs + value as f32
+  uint64_t *crec;
+  int32_t *xc;
+  int cwin, cmask;  // cwin 0 = off (also in launches where the cache is not live)
+  uint32_t cgen;
+  int cshared;  // 1: a follower lane using its leader's table (the leader inserts the rows it serves)
+  int served;  // 1: k_scan_need numbers down-2 / down-3 slots after the network rows (peer_on or the cache)
+  float *root_prior;
+  uint32_t *err;
+  // games
+  uint64_t *gpos, *gneg;
+  int32_t *gply;
+  uint8_t *gswap, *gstate;
+  int8_t *gresult;
+  int64_t *gid;
+  int8_t *mv_state;
+  float *mv_probs;
+  double *mv_q;
+  uint8_t *mv_qf64;
+  int32_t *mv_count;
+  int8_t *ex_state;
+  float *ex_probs;
+  double *ex_q;
+  uint8_t *ex_qf64;
+  float *ex_z;
+  int64_t *ex_game;
+  int32_t *ex_count;
+  int32_t ex_cap;
+  int64_t *gcnt;  // games counters: [0] finished [1..6] results [7] next id [8] limit [9] exported
+  int32_t *gscratch;
+  // per-tree players (two-network arenas, compare_models / evaluation games)
+  uint8_t *tnet;     // [T] network whose leaves this tree sends (0 / 1)
+  uint8_t *tkind;    // [T] SPMCTS_PLAYER_*: MCTS, or a hard-coded player (hardcoded_players.py)
+  int32_t *budget;   // [T] simulations per search of this tree (MCTreeSearch.iterations)
+  // per-tree search settings (each side of an evaluation game is built from its own container's
+  // kwargs, selfplayworker.py:71-81): Dirichlet alpha, strong_play, sims in flight (<= K)
+  double *talpha;
+  uint8_t *tstrong;
+  int32_t *tK;
+  int32_t seg1;      // first leaf row of network 1 (= number of network-0 trees)
+  int32_t record;    // games mode: keep Move records (play_episode update=True)
+  int32_t sim;       // index of the current simulation within the search (by value per launch)
+};
+
+// Node store.  A child block (the A children of one expanded node, P = APAD slots) is ONE contiguous
+// record of 32 * P bytes: n i32[P] | vl i32[P] | child-block i32[P] | p f32[P] | w f64[P] | f64 flag
+// u8[P] | valid-children mask u32 | pad.  The fields a select level scores (n, vl, child, p: the first
+// 16 P bytes; w, the mask: the next) lie in two 128-byte lines for Connect4 (P = 8) instead of one line
+// per field array.  Node id i = (tree * cap + block) * P + slot, as before; the flag is "w is a numpy
+// float64" (strong_play dtype quirk, mcts.py:287/:308), vl is MCNode.virtual_loss (mcts.py:44).
+template <int P>
+struct NodeRec {
+  static constexpr int N = 0, VL = 4 * P, C = 8 * P, PR = 12 * P, W = 16 * P, F = 24 * P, VM = 25 * P, BYTES = 32 * P;
+  static_assert(VM + 4 <= BYTES && W % 8 == 0 && VM % 4 == 0, "record layout");
+};
+template <int P>
+__host__ __device__ __forceinline__ char *nd_rec(const View &v, size_t i) {
+  return v.nodes + (i / P) * (size_t)NodeRec<P>::BYTES;
+}
+template <int P>
+__host__ __device__ __forceinline__ int32_t &nd_n(const View &v, size_t i) {
+  return ((int32_t *)(nd_rec<P>(v, i) + NodeRec<P>::N))[i % P];
+}
+template <int P>
+__host__ __device__ __forceinline__ int32_t &nd_vl(const View &v, size_t i) {
+  return ((int32_t *)(nd_rec<P>(v, i) + NodeRec<P>::VL))[i % P];
+}
+template <int P>
+__host__ __device__ __forceinline__ int32_t &nd_c(const View &v, size_t i) {
+  return ((int32_t *)(nd_rec<P>(v, i) + NodeRec<P>::C))[i % P];
+}
+template <int P>
+__host__ __device__ __forceinline__ float &nd_p(const View &v, size_t i) {
+  return ((float *)(nd_rec<P>(v, i) + NodeRec<P>::PR))[i % P];
+}
+template <int P>
+__host__ __device__ __forceinline__ double &nd_w(const View &v, size_t i) {
+  return ((double *)(nd_rec<P>(v, i) + NodeRec<P>::W))[i % P];
+}
+template <int P>
+__host__ __device__ __forceinline__ uint8_t &nd_f(const View &v, size_t i) {
+  return ((uint8_t *)(nd_rec<P>(v, i) + NodeRec<P>::F))[i % P];
+}
+// valid-children mask of block `gb` = tree * cap + block
+template <int P>
+__host__ __device__ __forceinline__ uint32_t &nd_vm(const View &v, size_t gb) {
+  return *(uint32_t *)(v.nodes + gb * (size_t)NodeRec<P>::BYTES + NodeRec<P>::VM);
+}
+
+enum { C_SIMS = 0, C_NN = 1, C_TERM = 2, C_DEPTH = 3, C_SETNODE = 4, C_MOVES = 5, C_LEAK = 6, C_GC = 7, C_HWM = 8, C_NCNT = 10 };
+enum { GS_IDLE = 0, GS_ACTIVE = 1, GS_DONE = 2 };
+
+__device__ __forceinline__ void set_err(const View &v, uint32_t f) { atomicOr(v.err, f); }
+
+template <class G>
+__device__ __forceinline__ size_t nbase(const View &v, int tree) {
+  return (size_t)tree * (size_t)v.cap * G::APAD;
+}

@@ -34,15 +34,6 @@
 
 namespace tower {
 
-// The weight ring's loads for the next layer's first DEPTH k-steps are issued unconditionally (the
-// last conv re-reads its own first steps, discarded): a conditional load made hipcc merge the ring
-// registers with copies at every layer's last k-step, behind an s_waitcnt vmcnt(0) that drained
-// the whole weight pipeline once per layer.
-#ifndef SPMCTS_RING_ALWAYS
-#define SPMCTS_RING_ALWAYS 1
-#endif
-constexpr bool kRingAlways = SPMCTS_RING_ALWAYS != 0;
-
 // edge-tile layout tables (tower_edge.h): row -> (board, x, y) packed (the inverse map,
 // EDGE_CELL_ROW_INIT, is used only by the host-side layout tests)
 constexpr uint16_t kEdgeRow[256] = EDGE_ROW_INIT;
@@ -127,11 +118,16 @@ struct Cfg : Ty<E_> {
   static constexpr int NT = ROWS / 32 / MG;  // 32-cell tiles per wave
   static constexpr int MT = C / 32 / CG;     // 32-channel tiles per wave
   static constexpr int BUF = (ROWS + NZ) * RS;
-  // Edge tiles (EDGE, a column-major-tile variant): rows ordered by tower_edge.h so that whole cell
-  // tiles hold only x = 0, y = 0, x = W-1 or y = H-1 cells; 12 of the workgroup's 72 (tile, tap)
-  // pairs read zero padding only and are skipped.  Neighbours are no longer affine row offsets:
-  // a 9 x ROWS table of neighbour rows (zero rows for off-board) sits in LDS after the buffers.
-  static constexpr bool EDGE = EDGE_ && XMAJ_;
+  // Row layout of the tile, one of two.  Board-major (default): row = board * CELLS + x * H + y; a neighbour
+  // is the affine row offset dx * DX + dy.  Edge tiles (EDGE): rows ordered by tower_edge.h so that whole cell
+  // tiles hold only x = 0, y = 0, x = W-1 or y = H-1 cells; 12 of the workgroup's 72 (tile, tap) pairs read
+  // zero padding only and are skipped, and neighbours come from a 9 x ROWS table of neighbour rows (zero rows
+  // for off-board) that sits in LDS after the buffers.  XMAJ_ (column-major across boards, the family the edge
+  // layout grew out of) only ever accompanies EDGE_.
+  static_assert(XMAJ_ == EDGE_, "two row layouts: board-major, or edge tiles (XMAJ_ and EDGE_ both set)");
+  static constexpr bool EDGE = EDGE_;
+  static constexpr bool XMAJ = XMAJ_;
+  static constexpr int DX = H;
   static constexpr int TAB = EDGE ? 9 * ROWS * 2 : 0;
   // ONEBUF (tower_wide.h): one activation buffer, convs in place between two barriers
   static constexpr bool ONEBUF = ONEBUF_;
@@ -145,23 +141,11 @@ struct Cfg : Ty<E_> {
   static_assert(LDS <= 163840, "LDS budget");
   static_assert(!EDGE_ || (W == 7 && H == 6 && ROWS == 256 && BOARDS == 6 && (MG == 2 || MG == 1)),
                 "edge layout: 6 Connect4 boards, two row halves or one");
-  // Row layout of the tile.  Board-major (default): row = board * CELLS + x * H + y.  Column-major
-  // across boards (XMAJ): row = x * (BOARDS * H) + board * H + y, so each board column x of all the
-  // tile's boards is BOARDS*H consecutive rows: with 6 boards (36 rows per column) cell tile 0 lies
-  // in column 0 and tile 7 in column 6, whose dx = -1 / +1 taps read only zero padding and are
-  // skipped: 6 of the 72 (tile, tap) pairs of the workgroup, 8.3 % of the MFMAs.
-  // A neighbour stays an affine row offset in both layouts: dx * DX + dy.
-  static constexpr bool XMAJ = XMAJ_;
-  static constexpr int DX = XMAJ ? BOARDS * H : H;
   // (board, x, y) of a row < VROWS
-  __host__ __device__ static constexpr int row_board(int row) {
-    return EDGE ? kEdgeRow[row] >> 6 : XMAJ ? (row / H) % BOARDS : row / CELLS;
-  }
-  __host__ __device__ static constexpr int row_x(int row) {
-    return EDGE ? (kEdgeRow[row] >> 3) & 7 : XMAJ ? row / (BOARDS * H) : (row % CELLS) / H;
-  }
+  __host__ __device__ static constexpr int row_board(int row) { return EDGE ? kEdgeRow[row] >> 6 : row / CELLS; }
+  __host__ __device__ static constexpr int row_x(int row) { return EDGE ? (kEdgeRow[row] >> 3) & 7 : (row % CELLS) / H; }
   __host__ __device__ static constexpr int row_y(int row) { return EDGE ? kEdgeRow[row] & 7 : row % H; }
-  // does row `row` (< ROWS) hold a cell?  Board-major / column-major tiles: rows < VROWS; edge tiles: the
+  // does row `row` (< ROWS) hold a cell?  Board-major tiles: rows < VROWS; edge tiles: the
   // rows tower_edge.h does not mark as padding (255), which may sit anywhere in the tile
   __host__ __device__ static constexpr bool row_ok(int row) { return EDGE ? kEdgeRow[row] != 255 : row < VROWS; }
   // does any on-board row of cell tile T have an on-board neighbour for `tap`?
@@ -358,7 +342,7 @@ __device__ __forceinline__ void acc_store_relu(const f32x16 (&acc)[K::MT][K::NT]
 template <class K, int KK, int DEPTH, bool RESID>
 __device__ __forceinline__ void conv_layer(const char *src, char *dst, const Nbr<K> &nb, bf16x8 (&a)[DEPTH][K::MT],
                                            const float *bias, int wave, int lane, const WBuf &wb, uint32_t wl_off,
-                                           uint32_t wn_off, int wn_steps) {
+                                           uint32_t wn_off) {
   // wl_off / wn_off: byte offset of (this layer / next layer, this wave's first channel tile, step 0);
   // channel tile m adds m * 9 * KK fragments of 1 KiB, step s adds s KiB
   constexpr uint32_t MSTRIDE = 9u * KK * 1024u;
@@ -405,7 +389,11 @@ __device__ __forceinline__ void conv_layer(const char *src, char *dst, const Nbr
       if (sn < STEPS) {
 #pragma unroll
         for (int m = 0; m < K::MT; ++m) a[slot][m] = wb.load(wl_off + m * MSTRIDE + (uint32_t)sn * 1024u);
-      } else if (kRingAlways || sn - STEPS < wn_steps) {
+      } else {
+        // The weight ring's loads for the next layer's first DEPTH k-steps are issued unconditionally (the
+        // last conv re-reads its own first steps, discarded): a conditional load made hipcc merge the ring
+        // registers with copies at every layer's last k-step, behind an s_waitcnt vmcnt(0) that drained
+        // the whole weight pipeline once per layer.
 #pragma unroll
         for (int m = 0; m < K::MT; ++m) a[slot][m] = wb.load(wn_off + m * MSTRIDE + (uint32_t)(sn - STEPS) * 1024u);
       }
@@ -445,10 +433,9 @@ __device__ __forceinline__ void conv_layer(const char *src, char *dst, const Nbr
   acc_store_bias_relu_pre<K, RESID>(acc, dst, bv, wave, lane);
 }
 
-// Per-tap live cell tiles of a column-major / edge-tile layer (Cfg::XMAJ, Cfg::EDGE) for the waves of row
-// group MG_: a tile all of whose rows lie in board column 0 (dx = -1) or W-1 (dx = +1), or whose taps read
-// zero padding only (edge tiles), would multiply zeros; its MFMAs and operand reads are skipped (the
-// skipped contributions are exact zeros).  Used by the 16x16x32 trunks (tower_m16.h, tower_wide16.h).
+// Per-tap live cell tiles of an edge-tile layer (Cfg::EDGE) for the waves of row group MG_: a tile whose
+// taps read zero padding only would multiply zeros; its MFMAs and operand reads are skipped (the skipped
+// contributions are exact zeros).  Used by the 16x16x32 trunks (tower_m16.h, tower_wide16.h).
 template <class K, int MG_>
 struct XLive {
   static constexpr uint32_t popc(uint32_t m) { return m ? (m & 1u) + popc(m >> 1) : 0u; }
@@ -632,14 +619,13 @@ __device__ __forceinline__ void tower_tile(char *smem, const __bf16 *planes, int
   const uint32_t ct0_off = (uint32_t)(STEM + (size_t)((wave_u % K::CG) * K::MT) * LSTEPS * 64) * 16u;
   for (int L = 0; L < n_convs; ++L) {
     const uint32_t wl_off = ct0_off + (uint32_t)((size_t)L * LAYER * 16u);
-    const uint32_t wn_off = (kRingAlways && L + 1 == n_convs) ? wl_off : wl_off + (uint32_t)(LAYER * 16u);
-    const int wn_steps = L + 1 < n_convs ? LSTEPS : 0;
+    const uint32_t wn_off = L + 1 == n_convs ? wl_off : wl_off + (uint32_t)(LAYER * 16u);
     static_assert(K::M16 || K::ONEBUF || !K::XMAJ,
                   "the 32x32x16 trunk is board-major (the column-group tiles: tower_m16.h, tower_wide16.h)");
     if ((L & 1) == 0) {
-      conv_layer<K, KK, DEPTH, false>(X, Y, nb, ring, b, wave, lane, wb, wl_off, wn_off, wn_steps);
+      conv_layer<K, KK, DEPTH, false>(X, Y, nb, ring, b, wave, lane, wb, wl_off, wn_off);
     } else {
-      conv_layer<K, KK, DEPTH, true>(Y, X, nb, ring, b, wave, lane, wb, wl_off, wn_off, wn_steps);
+      conv_layer<K, KK, DEPTH, true>(Y, X, nb, ring, b, wave, lane, wb, wl_off, wn_off);
     }
     b += K::C;
     __syncthreads();
@@ -666,7 +652,7 @@ __host__ __device__ __forceinline__ int tail_kind(int rem, int cus) {
 }
 
 // Device-count driven variant: the batch size is read from device memory (the arena's leaf-row
-// counter), so the host never waits for it.  Workgroups are assigned as in launch_split: whole
+// counter), so the host never waits for it.  Workgroups are assigned in whole
 // chip rounds of full-size tiles, then the remainder in one round of the smallest tile that covers
 // it (tail_kind); surplus workgroups of the (maximum-size) grid exit at once.
 template <class KF, class KM, class KH>
@@ -705,300 +691,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
 }
 
-// ---------------------------------------------------------------------------------------
-// Linear heads (modules.py:96-105 after the 1x1 convs), fused, for BOARDS boards per workgroup:
-//   policy = softmax(pf @ Wp^T + bp)          pf = features[:, :, :ff]  (cell-major, K = cells*ff)
-//   value  = tanh(relu(vf @ Wv^T + bv) @ wo + bo)                     vf = features[:, :, ff:]
-// on v_mfma_f32_32x32x16_bf16 (M = 32 rows of which BOARDS are boards, N = 32 weight rows).
-// The workgroup's features are staged once into LDS (coalesced; per-board stride padded by 16 B
-// so the 16-B operand reads of 16 different boards are bank-conflict free); weight fragments are
-// pre-swizzled on the host (one contiguous KiB per (32-row tile, 16-k step): lane (r, h) holds
-// W[tile*32 + r][16 s + 8 h .. + 8]) and streamed through a 4-deep register ring.  Wave w owns
-// value tiles [w*VTW, (w+1)*VTW) over all of K and the policy tile over a quarter of K; partial
-// sums are combined in a fixed order (deterministic, batch-independent).
-// Weight blob: tile 0 = Wp padded to 32 rows, tiles 1..VT = Wv; float blob: bp[32], bv[8ff], wo[8ff], bo.
-template <int FF, int CELLS, int A>
-struct HeadsCfg {
-  static constexpr int K = CELLS * FF, KS = K / 16, HID = 8 * FF, VT = HID / 32, VTW = VT / 4;
-  static constexpr int FROW = CELLS * 2 * FF * 2;  // feature bytes per board
-  static constexpr int BOARDS = FROW * 16 + 16 * 16 <= 96 * 1024 ? 16 : 8;
-  static constexpr int FS = FROW + 16;             // LDS stride per board
-  static constexpr int KQ = (KS + 3) / 4;          // policy k-steps per wave
-  static_assert(VT % 4 == 0 && FF % 16 == 0 && FROW % 16 == 0, "head tile plan");
-};
-
-template <int FF, int CELLS, int A, class E = __bf16>
-__global__ __launch_bounds__(256) void k_heads(const uint16_t *feats, int n, const int32_t *count, const bf16x8 *wf,
-                                               const float *hb, float *probs, float *values) {
-  using H = HeadsCfg<FF, CELLS, A>;
-  if (count) n = min(*count, n);  // n = the caller's buffer rows
-  const int b0 = blockIdx.x * H::BOARDS;
-  if (b0 >= n) return;
-  __shared__ __attribute__((aligned(16))) char s_feat[H::BOARDS * H::FS];
-  __shared__ float s_part[4][32];        // per-wave value partial sums
-  __shared__ float s_pol[4][32][33];     // per-wave policy partial logits
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-  const int nb = min(H::BOARDS, n - b0);
-  // stage the features of this workgroup's boards (16 B per thread-iteration, coalesced)
-  {
-    constexpr int CH = H::FROW / 16;
-    const uint4 *src = (const uint4 *)(feats + (size_t)b0 * CELLS * 2 * FF);
-    for (int i = tid; i < H::BOARDS * CH; i += 256) {
-      const int bd = i / CH, c = i % CH;
-      const uint4 v = bd < nb ? src[(size_t)bd * CH + c] : make_uint4(0, 0, 0, 0);
-      *(uint4 *)(s_feat + bd * H::FS + c * 16) = v;
-    }
-  }
-  const float *bp = hb, *bv = hb + 32, *wo = hb + 32 + H::HID, *bo = hb + 32 + 2 * H::HID;
-  const int row = r % H::BOARDS;  // rows >= BOARDS duplicate a board; their results are ignored
-  const char *frow = s_feat + row * H::FS;
-  f32x16 acc[H::VTW];
-  f32x16 pacc = {};
-#pragma unroll
-  for (int v = 0; v < H::VTW; ++v) acc[v] = f32x16{};
-  // weight ring: VTW value fragments (+ 1 policy fragment while s is in this wave's quarter)
-  constexpr int D = 4;
-  bf16x8 ring[D][H::VTW];
-  const bf16x8 *wv = wf + (size_t)(1 + wave * H::VTW) * H::KS * 64 + lane;
-  const bf16x8 *wp = wf + lane;
-  const int q0 = wave * H::KQ, q1 = min(H::KS, q0 + H::KQ);
-  __syncthreads();
-#pragma unroll
-  for (int d = 0; d < D; ++d)
-#pragma unroll
-    for (int v = 0; v < H::VTW; ++v) ring[d][v] = wv[((size_t)v * H::KS + d) * 64];
-  bf16x8 pnext = wp[(size_t)q0 * 64];
-  for (int s0 = 0; s0 < H::KS; s0 += D) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      const int s = s0 + d;
-      if (s >= H::KS) break;
-      const int k0 = 16 * s + 8 * h;
-      const int cell = k0 / FF, c = k0 % FF;
-      const bf16x8 av = *(const bf16x8 *)(frow + (cell * 2 * FF + FF + c) * 2);
-      bf16x8 wcur[H::VTW];
-#pragma unroll
-      for (int v = 0; v < H::VTW; ++v) {
-        wcur[v] = ring[d][v];
-        if (s + D < H::KS) ring[d][v] = wv[((size_t)v * H::KS + s + D) * 64];
-      }
-#pragma unroll
-      for (int v = 0; v < H::VTW; ++v) acc[v] = Ty<E>::mfma(av, wcur[v], acc[v]);
-      if (s >= q0 && s < q1) {
-        const bf16x8 ap = *(const bf16x8 *)(frow + (cell * 2 * FF + c) * 2);
-        const bf16x8 pw = pnext;
-        if (s + 1 < q1) pnext = wp[(size_t)(s + 1) * 64];
-        pacc = Ty<E>::mfma(ap, pw, pacc);
-      }
-    }
-  }
-  // value: relu(acc + bv[col]) * wo[col], summed over the hidden units (cols)
-  // D layout: lane (r, h): col = r, rows (boards) = (i & 3) + 8 * (i >> 2) + 4 * h
-  float part[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) part[i] = 0.f;
-#pragma unroll
-  for (int v = 0; v < H::VTW; ++v) {
-    const int col = (wave * H::VTW + v) * 32 + r;
-    const float bb = bv[col], ww = wo[col];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) part[i] += fmaxf(acc[v][i] + bb, 0.f) * ww;
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    float x = part[i];
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) x += __shfl_xor(x, off, 32);
-    part[i] = x;
-  }
-  if (r == 0) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s_part[wave][(i & 3) + 8 * (i >> 2) + 4 * h] = part[i];
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) s_pol[wave][(i & 3) + 8 * (i >> 2) + 4 * h][r] = pacc[i];
-  __syncthreads();
-  if (tid < nb) {
-    const int bd = b0 + tid;
-    values[bd] = tanhf(((s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid])) + bo[0]);
-    float lg[A];
-    float m = -INFINITY;
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-      lg[a] = ((s_pol[0][tid][a] + s_pol[1][tid][a]) + (s_pol[2][tid][a] + s_pol[3][tid][a])) + bp[a];
-      m = fmaxf(m, lg[a]);
-    }
-    float e[A], sum = 0.f;
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-      e[a] = __expf(lg[a] - m);
-      sum += e[a];
-    }
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int a = 0; a < A; ++a) probs[(size_t)bd * A + a] = e[a] * inv;
-  }
-}
-
-// k_heads with room beside a trunk workgroup.  The trunk holds 152.5 KB of a CU's 160 KB LDS and
-// 416 of each SIMD's 512 registers per lane, so k_heads (86 KB of staged features) could only run on
-// a CU no trunk workgroup occupies: its 512 workgroups waited for the other lane's trunk workgroups
-// to retire (0.8-1 ms per call in the bench against 11 us alone), and the lane's expand and next
-// trunk launch waited behind it.  This form reads the features straight from global memory (L2:
-// the trunk wrote them just before) as the MFMA A operand, fills all 32 MFMA rows with boards (32
-// per workgroup, half the weight traffic of 16), keeps only the cross-wave sums in LDS (4.6 KB), and
-// is held to 96 registers per lane, so one wave fits on each SIMD beside a trunk wave.  Same math
-// in the same order as k_heads (per-wave k order, fixed-order cross-wave sums): bit-identical.
-//
-// C = 256 (FF = 64: 4 value tiles per wave, which spill at 96 registers in one pass) runs the value
-// tiles in two passes of 2 over all of K (the features are read twice, from L2) within the same 96
-// registers; the C = 256 trunk wave uses 400 of a SIMD's 512, so one heads wave fits beside it.
-// part[] still sums the tiles in order 0..3: bit-identical.
-template <int FF, int CELLS, int A, class E = __bf16, int WPE = 5, int VP = HeadsCfg<FF, CELLS, A>::VTW>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_heads_co(
-    const uint16_t *feats, int n, const int32_t *count, const bf16x8 *wf, const float *hb, float *probs, float *values) {
-  using H = HeadsCfg<FF, CELLS, A>;
-  static_assert(H::VTW % VP == 0, "value tiles per pass");
-  constexpr int BOARDS = 32;
-  if (count) n = min(*count, n);  // n = the caller's buffer rows
-  const int b0 = blockIdx.x * BOARDS;
-  if (b0 >= n) return;
-  __shared__ float s_part[4][BOARDS];     // per-wave value partial sums
-  constexpr int AP = (A + 7) / 8 * 8;
-  __shared__ float s_pol[4][BOARDS][AP];  // per-wave policy partial logits
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-  const int nb = min(BOARDS, n - b0);
-  const float *bp = hb, *bv = hb + 32, *wo = hb + 32 + H::HID, *bo = hb + 32 + 2 * H::HID;
-  // row r = board b0 + r (rows past the batch repeat its last board; their results are not stored)
-  const char *frow = (const char *)feats + (size_t)(b0 + min(r, nb - 1)) * H::FROW;
-  // value tiles first, then the policy quarter (each in k_heads' per-wave k order): only one set of
-  // accumulators is live at a time, which keeps the wave inside 96 registers without spills
-  const bf16x8 *wp = wf + lane;
-  const int q0 = wave * H::KQ, q1 = min(H::KS, q0 + H::KQ);
-  // the features of step s (value half at FF, policy half at 0), one step ahead
-  auto feat = [&](int s, int half) {
-    const int k0 = 16 * s + 8 * h;
-    return *(const bf16x8 *)(frow + ((k0 / FF) * 2 * FF + half + k0 % FF) * 2);
-  };
-  float part[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) part[i] = 0.f;
-#pragma unroll 1
-  for (int v0 = 0; v0 < H::VTW; v0 += VP) {
-    f32x16 acc[VP];
-#pragma unroll
-    for (int v = 0; v < VP; ++v) acc[v] = f32x16{};
-    constexpr int D = 2;  // weight ring depth
-    bf16x8 ring[D][VP];
-    const bf16x8 *wv = wf + (size_t)(1 + wave * H::VTW + v0) * H::KS * 64 + lane;
-#pragma unroll
-    for (int d = 0; d < D; ++d)
-#pragma unroll
-      for (int v = 0; v < VP; ++v) ring[d][v] = wv[((size_t)v * H::KS + d) * 64];
-    bf16x8 avn = feat(0, FF);
-    for (int s0 = 0; s0 < H::KS; s0 += D) {
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        const int s = s0 + d;
-        if (s >= H::KS) break;
-        const bf16x8 av = avn;
-        if (s + 1 < H::KS) avn = feat(s + 1, FF);
-        bf16x8 wcur[VP];
-#pragma unroll
-        for (int v = 0; v < VP; ++v) {
-          wcur[v] = ring[d][v];
-          if (s + D < H::KS) ring[d][v] = wv[((size_t)v * H::KS + s + D) * 64];
-        }
-#pragma unroll
-        for (int v = 0; v < VP; ++v) acc[v] = Ty<E>::mfma(av, wcur[v], acc[v]);
-      }
-    }
-    // value: relu(acc + bv[col]) * wo[col], summed over the hidden units (cols); as k_heads
-#pragma unroll
-    for (int v = 0; v < VP; ++v) {
-      const int col = (wave * H::VTW + v0 + v) * 32 + r;
-      const float bb = bv[col], ww = wo[col];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) part[i] += fmaxf(acc[v][i] + bb, 0.f) * ww;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    float x = part[i];
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) x += __shfl_xor(x, off, 32);
-    part[i] = x;
-  }
-  if (r == 0) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s_part[wave][(i & 3) + 8 * (i >> 2) + 4 * h] = part[i];
-  }
-  f32x16 pacc = {};
-  if (q0 < q1) {
-    bf16x8 pn = wp[(size_t)q0 * 64], apn = feat(q0, 0);
-    for (int s = q0; s < q1; ++s) {
-      const bf16x8 pw = pn, ap = apn;
-      if (s + 1 < q1) {
-        pn = wp[(size_t)(s + 1) * 64];
-        apn = feat(s + 1, 0);
-      }
-      pacc = Ty<E>::mfma(ap, pw, pacc);
-    }
-  }
-  if (r < A) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s_pol[wave][(i & 3) + 8 * (i >> 2) + 4 * h][r] = pacc[i];
-  }
-  __syncthreads();
-  if (tid < nb) {
-    const int bd = b0 + tid;
-    values[bd] = tanhf(((s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid])) + bo[0]);
-    float lg[A];
-    float m = -INFINITY;
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-      lg[a] = ((s_pol[0][tid][a] + s_pol[1][tid][a]) + (s_pol[2][tid][a] + s_pol[3][tid][a])) + bp[a];
-      m = fmaxf(m, lg[a]);
-    }
-    float e[A], sum = 0.f;
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-      e[a] = __expf(lg[a] - m);
-      sum += e[a];
-    }
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int a = 0; a < A; ++a) probs[(size_t)bd * A + a] = e[a] * inv;
-  }
-}
-
-// Head epilogue after one GEMM  Z = features[n][cells*2ff] @ Wc^T  (Wc = value rows [8ff]
-// then policy rows [A], zero where a row meets the other head's channels):
-//   value = tanh(sum_j relu(Z[j] + bv[j]) * wo[j] + bo), probs = softmax(Z[8ff + a] + bp[a]).
-// One wave per board; the hidden-unit sum is a fixed-order lane reduction (deterministic).
-template <int HID, int A>
-__global__ __launch_bounds__(256) void k_head_epilogue(const __bf16 *Z, int ldz, int n, const float *hb,
-                                                       float *probs, float *values) {
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-  if (wave >= n) return;
-  const __bf16 *z = Z + (size_t)wave * ldz;
-  const float *bv = hb, *wo = hb + HID, *bo = hb + 2 * HID, *bp = hb + 2 * HID + 1;
-  float acc = 0.f;
-#pragma unroll
-  for (int j = lane; j < HID; j += 64) acc += fmaxf((float)z[j] + bv[j], 0.f) * wo[j];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  float logit = lane < A ? (float)z[HID + lane] + bp[lane] : -INFINITY;
-  float m = logit;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  const float e = lane < A ? __expf(logit - m) : 0.f;
-  float sum = e;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-  if (lane < A) probs[(size_t)wave * A + lane] = e / sum;
-  if (lane == 0) values[wave] = tanhf(acc + bo[0]);
-}
+#include "tower_heads.h"
 
 // Residual scratch of the one-buffer trunk (tower_wide.h): one region per workgroup of a launch, one
 // buffer per stream (launches on different streams run concurrently), grown on demand.
@@ -1063,29 +756,6 @@ static int num_cus() {
       n = 256;
   }
   return n;
-}
-
-// Full-size workgroups (one per CU, BOARDS boards each) for whole rounds of the chip, then the
-// remainder in one round of the smallest tile that covers it (tail_kind: half-size tiles take about
-// half the time, 4-board tiles three quarters): a batch of 3,700 boards costs 2.5 workgroup-rounds
-// instead of 3, one of 4,096 boards 2.75.
-template <class KF, class KM, class KH>
-static int launch_split(const char *planes, int batch, int n_blocks, const void *w, const float *b, char *out,
-                        hipStream_t s) {
-  const int cus = num_cus();
-  const int full_wgs = (batch / KF::BOARDS) / cus * cus;
-  const int n_full = full_wgs * KF::BOARDS;
-  const int rem = batch - n_full;
-  int rc = 0;
-  if (n_full > 0) rc = launch<KF>(planes, n_full, n_blocks, w, b, out, s);
-  if (rc || rem <= 0) return rc;
-  const char *p2 = planes + (size_t)n_full * KF::CELLS * 3 * 2;
-  char *o2 = out + (size_t)n_full * KF::CELLS * KF::HEAD * 2;
-  switch (tail_kind<KF, KM, KH>(rem, cus)) {
-    case 0: return launch<KH>(p2, rem, n_blocks, w, b, o2, s);
-    case 1: return launch<KM>(p2, rem, n_blocks, w, b, o2, s);
-    default: return launch<KF>(p2, rem, n_blocks, w, b, o2, s);
-  }
 }
 
 // pack: the launch runs beside launches on other streams (SPMCTS_TOWER_PACK): tiles are assigned
@@ -1156,60 +826,68 @@ static int ab_switch_guard() {
 #endif
 }
 
-// the instantiated tile sets of the device-count path, per board shape, channels and element type
+// The product tile sets, each written out once: F / M / H = the full / middle / half tiles of the device-count
+// path (k_tower_dyn: whole rounds of F, the tail in the smallest that covers it); the host-count path (k_tower)
+// runs F alone.  A = the game's action count on that board (the policy head's width).
+template <int A_, class F_, class M_ = F_, class H_ = F_>
+struct TileSet {
+  static constexpr int A = A_;
+  using F = F_;
+  using M = M_;
+  using H = H_;
+};
+// 7x6, C = 128: 16x16x32 edge tiles for every board, tails included (tower_m16.h)
+template <class E>
+using Tiles7x6c128 = TileSet<7, Cfg<128, 256, 7, 6, 2, 4, 2, 1, true, true, E, false, true>>;
+// 7x6, C = 256: every tile a 6-board one-buffer 16x16x32 tile (tower_wide16.h; a batch tail takes one partly
+// empty tile), so every board goes through the same arithmetic
+template <class E>
+using Tiles7x6c256 = TileSet<7, Cfg<256, 256, 7, 6, 4, 4, 2, 1, true, true, E, true, true>>;
+#ifdef SPMCTS_AB
+// SPMCTS_TOWER_C256=3: 7x6, C = 256 on 3-board two-buffer tiles (32x32x16 layout)
+template <class E>
+using Tiles7x6c256Board3 = TileSet<7, Cfg<256, 128, 7, 6, 4, 4, 4, 1, false, false, E>>;
+#endif
+template <class E>
+using Tiles3x3c128 = TileSet<9, Cfg<128, 256, 3, 3, 2, 4, 4, 1, false, false, E>, Cfg<128, 192, 3, 3, 2, 4, 4, 1, false, false, E>,
+                             Cfg<128, 128, 3, 3, 2, 4, 4, 1, false, false, E>>;
+template <class E>
+using Tiles3x3c256 = TileSet<9, Cfg<256, 128, 3, 3, 4, 4, 4, 1, false, false, E>>;
+
+// The one (width, height, channels) switch: f(the shape's tile set for element type E), or -2.
+template <class E, class Fn>
+static int with_tiles(int32_t width, int32_t height, int32_t channels, Fn &&f) {
+  if (channels != 128 && channels != 256) return -2;
+  if (width == 7 && height == 6) {
+    if (channels == 128) return f(Tiles7x6c128<E>{});
+#ifdef SPMCTS_AB
+    if (c256_board3()) return f(Tiles7x6c256Board3<E>{});
+#endif
+    return f(Tiles7x6c256<E>{});
+  }
+  if (width == 3 && height == 3) return channels == 128 ? f(Tiles3x3c128<E>{}) : f(Tiles3x3c256<E>{});
+  return -2;
+}
+
+// the device-count path
 template <class E>
 static int forward_dev(int32_t width, int32_t height, int32_t channels, int32_t n_blocks, const void *planes_dev,
                        const int32_t *count_dev, int32_t max_batch, const void *weights_dev, const float *bias_dev,
                        void *features_dev, bool pack, hipStream_t s) {
-  if (width == 7 && height == 6 && channels == 128) {
-    // 16x16x32 edge tiles for every board, tails included (tower_m16.h)
-    using KM = Cfg<128, 256, 7, 6, 2, 4, 2, 1, true, true, E, false, true>;
-    return launch_dyn<KM, KM, KM>(planes_dev, count_dev, max_batch, n_blocks, weights_dev, bias_dev, features_dev, pack, s);
-  }
-  if (width == 7 && height == 6 && channels == 256) {
-#ifdef SPMCTS_AB
-    using K3 = Cfg<256, 128, 7, 6, 4, 4, 4, 1, false, false, E>;
-    if (c256_board3())
-      return launch_dyn<K3, K3, K3>(planes_dev, count_dev, max_batch, n_blocks, weights_dev, bias_dev, features_dev, pack, s);
-#endif
-    // every tile a 6-board one-buffer 16x16x32 tile (tower_wide16.h; a batch tail takes one partly empty tile),
-    // so every board goes through the same arithmetic
-    using KW16 = Cfg<256, 256, 7, 6, 4, 4, 2, 1, true, true, E, true, true>;
-    return launch_dyn<KW16, KW16, KW16>(planes_dev, count_dev, max_batch, n_blocks, weights_dev, bias_dev, features_dev,
-                                        pack, s);
-  }
-  if (width == 3 && height == 3 && channels == 128)
-    return launch_dyn<Cfg<128, 256, 3, 3, 2, 4, 4, 1, false, false, E>, Cfg<128, 192, 3, 3, 2, 4, 4, 1, false, false, E>,
-                      Cfg<128, 128, 3, 3, 2, 4, 4, 1, false, false, E>>(planes_dev, count_dev, max_batch, n_blocks,
-                                                                          weights_dev, bias_dev, features_dev, pack, s);
-  if (width == 3 && height == 3 && channels == 256)
-    return launch_dyn<Cfg<256, 128, 3, 3, 4, 4, 4, 1, false, false, E>, Cfg<256, 128, 3, 3, 4, 4, 4, 1, false, false, E>,
-                      Cfg<256, 128, 3, 3, 4, 4, 4, 1, false, false, E>>(planes_dev, count_dev, max_batch, n_blocks,
-                                                                          weights_dev, bias_dev, features_dev, pack, s);
-  return -2;
+  return with_tiles<E>(width, height, channels, [&](auto t) {
+    using T = decltype(t);
+    return launch_dyn<typename T::F, typename T::M, typename T::H>(planes_dev, count_dev, max_batch, n_blocks, weights_dev,
+                                                                   bias_dev, features_dev, pack, s);
+  });
 }
 
-// the host-count path (a batch size known on the host): the same tile sets, split on the host
+// the host-count path (a batch size known on the host)
 template <class E>
 static int forward_host(int32_t width, int32_t height, int32_t channels, int32_t n_blocks, const char *pl, int32_t batch,
                         const void *weights_dev, const float *bias_dev, char *ft, hipStream_t s) {
-  if (width == 7 && height == 6 && channels == 128) {
-    using KM = Cfg<128, 256, 7, 6, 2, 4, 2, 1, true, true, E, false, true>;
-    return launch<KM>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-  }
-  if (width == 7 && height == 6 && channels == 256) {
-#ifdef SPMCTS_AB
-    using K3 = Cfg<256, 128, 7, 6, 4, 4, 4, 1, false, false, E>;
-    if (c256_board3()) return launch<K3>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-#endif
-    return launch<Cfg<256, 256, 7, 6, 4, 4, 2, 1, true, true, E, true, true>>(pl, batch, n_blocks, weights_dev, bias_dev,
-                                                                                 ft, s);
-  }
-  if (width == 3 && height == 3 && channels == 128)
-    return launch<Cfg<128, 256, 3, 3, 2, 4, 4, 1, false, false, E>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-  if (width == 3 && height == 3 && channels == 256)
-    return launch<Cfg<256, 128, 3, 3, 4, 4, 4, 1, false, false, E>>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
-  return -2;
+  return with_tiles<E>(width, height, channels, [&](auto t) {
+    return launch<typename decltype(t)::F>(pl, batch, n_blocks, weights_dev, bias_dev, ft, s);
+  });
 }
 }  // namespace tower
 
@@ -1254,37 +932,23 @@ static int tower_heads(int32_t width, int32_t height, int32_t channels, int32_t 
   if (const int g = ab_switch_guard()) return g;
   // the co-resident k_heads_co (C = 256, FF = 64: two value passes of 2 tiles in 96 registers, beside the
   // C = 256 trunk); the A/B library's SPMCTS_HEADS=lds / SPMCTS_HEADS_C256=lds select the LDS-staged k_heads
-#define HEADS_CO(FF, CELLS, A)                                                                              \
-  hipLaunchKernelGGL((k_heads_co<FF, CELLS, A, E, 5, FF == 64 ? 2 : HeadsCfg<FF, CELLS, A>::VTW>),          \
-                     dim3((batch + 31) / 32), dim3(256), 0, s, (const uint16_t *)features_dev, batch,       \
-                     count_dev, (const bf16x8 *)head_w_dev, head_b_dev, probs_dev, values_dev)
+  return with_tiles<E>(width, height, channels, [&](auto t) {
+    using T = decltype(t);
+    constexpr int FF = T::F::C / 4, CELLS = T::F::CELLS, A = T::A;
+    using H = HeadsCfg<FF, CELLS, A>;
+    if (actions != A) return -2;
+    if (heads_co() && (FF == 32 || heads_co256()))
+      hipLaunchKernelGGL((k_heads_co<FF, CELLS, A, E, 5, FF == 64 ? 2 : H::VTW>), dim3((batch + 31) / 32), dim3(256), 0, s,
+                         (const uint16_t *)features_dev, batch, count_dev, (const bf16x8 *)head_w_dev, head_b_dev,
+                         probs_dev, values_dev);
 #ifdef SPMCTS_AB
-#define HEADS(FF, CELLS, A)                                                                                 \
-  do {                                                                                                      \
-    if (heads_co() && (FF == 32 || heads_co256()))                                                         \
-      HEADS_CO(FF, CELLS, A);                                                                               \
-    else                                                                                                    \
-      hipLaunchKernelGGL((k_heads<FF, CELLS, A, E>), dim3((batch + HeadsCfg<FF, CELLS, A>::BOARDS - 1) /    \
-                                                       HeadsCfg<FF, CELLS, A>::BOARDS), dim3(256), 0, s,     \
-                         (const uint16_t *)features_dev, batch, count_dev, (const bf16x8 *)head_w_dev,      \
-                         head_b_dev, probs_dev, values_dev);                                                \
-  } while (0)
-#else
-#define HEADS(FF, CELLS, A) HEADS_CO(FF, CELLS, A)
+    else
+      hipLaunchKernelGGL((k_heads<FF, CELLS, A, E>), dim3((batch + H::BOARDS - 1) / H::BOARDS), dim3(256), 0, s,
+                         (const uint16_t *)features_dev, batch, count_dev, (const bf16x8 *)head_w_dev, head_b_dev,
+                         probs_dev, values_dev);
 #endif
-  if (width == 7 && height == 6 && actions == 7 && channels == 128)
-    HEADS(32, 42, 7);
-  else if (width == 7 && height == 6 && actions == 7 && channels == 256)
-    HEADS(64, 42, 7);
-  else if (width == 3 && height == 3 && actions == 9 && channels == 128)
-    HEADS(32, 9, 9);
-  else if (width == 3 && height == 3 && actions == 9 && channels == 256)
-    HEADS(64, 9, 9);
-  else
-    return -2;
-#undef HEADS
-#undef HEADS_CO
-  return hipGetLastError() == hipSuccess ? 0 : -11;
+    return hipGetLastError() == hipSuccess ? 0 : -11;
+  });
 }
 
 extern "C" int spmcts_tower_heads(int32_t width, int32_t height, int32_t channels, int32_t actions,
@@ -1331,13 +995,11 @@ extern "C" int spmcts_head_epilogue(int32_t hidden, int32_t actions, const void 
 }
 
 extern "C" int spmcts_tower_supported(int32_t width, int32_t height, int32_t channels) {
-  return ((width == 7 && height == 6) || (width == 3 && height == 3)) && (channels == 128 || channels == 256);
+  return tower::with_tiles<__bf16>(width, height, channels, [](auto) { return 1; }) == 1;
 }
 
 extern "C" int spmcts_tower_weight_layout(int32_t width, int32_t height, int32_t channels) {
-  using namespace tower;
-  if (!spmcts_tower_supported(width, height, channels)) return -2;
-  if (width == 7 && height == 6 && channels == 128) return SPMCTS_WLAYOUT_M16;
-  if (width == 7 && height == 6 && channels == 256 && !c256_board3()) return SPMCTS_WLAYOUT_M16;
-  return SPMCTS_WLAYOUT_32X32;
+  return tower::with_tiles<__bf16>(width, height, channels, [](auto t) {
+    return decltype(t)::F::M16 ? SPMCTS_WLAYOUT_M16 : SPMCTS_WLAYOUT_32X32;
+  });
 }

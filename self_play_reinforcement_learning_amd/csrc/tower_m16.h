@@ -1,6 +1,6 @@
 // tower_m16.h — the C = 128 Connect4 trunk on v_mfma_f32_16x16x32_{bf16,f16} (round 4).
 //
-// Included by tower.hip (namespace tower): uses Cfg (M16), Nbr, XLive, WBuf, lds_b128, kRingAlways,
+// Included by tower.hip (namespace tower): uses Cfg (M16), Nbr, XLive, WBuf, lds_b128,
 // stem_layer's k-loop shape and head_layer from there.
 //
 // The same workgroup plan as the 32x32x16 edge-tile trunk (6 boards in 256 edge-ordered rows, two LDS
@@ -76,7 +76,7 @@ template <class K, int KK32, int DEPTH, int MG_, int TAP>
 __device__ __forceinline__ void conv_tap(const char *src, const Nbr<K> &nb, f32x4 (&acc)[MM<K>][K::NT][2],
                                          bf16x8 (&bc)[K::NT][2], bf16x8 (&bn)[K::NT][2], int (&off_cur)[K::NT][2],
                                          int (&off_nxt)[K::NT][2], bf16x8 (&a)[DEPTH][MM<K>], int qoff, int rb,
-                                         const WBuf &wb, uint32_t wl_off, uint32_t wn_off, int wn_steps) {
+                                         const WBuf &wb, uint32_t wl_off, uint32_t wn_off) {
   using X = XLive<K, MG_>;
   constexpr int NM = MM<K>;
   constexpr uint32_t MSTRIDE = 9u * KK32 * 1024u;  // bytes between a wave's 16-channel tiles
@@ -122,7 +122,7 @@ __device__ __forceinline__ void conv_tap(const char *src, const Nbr<K> &nb, f32x
     if (sn < STEPS) {
 #pragma unroll
       for (int mm = 0; mm < NM; ++mm) a[slot][mm] = wb.load(wl_off + mm * MSTRIDE + (uint32_t)sn * 1024u);
-    } else if (kRingAlways || sn - STEPS < wn_steps) {
+    } else {  // unconditional, the last layer included (see conv_layer in tower.hip)
 #pragma unroll
       for (int mm = 0; mm < NM; ++mm) a[slot][mm] = wb.load(wn_off + mm * MSTRIDE + (uint32_t)(sn - STEPS) * 1024u);
     }
@@ -206,7 +206,7 @@ __device__ __forceinline__ void epilogue(const f32x4 (&acc)[MM<K>][K::NT][2], ch
 template <class K, int KK32, int DEPTH, bool RESID, int MG_>
 __device__ __forceinline__ void conv_layer(const char *src, char *dst, const Nbr<K> &nb, bf16x8 (&a)[DEPTH][MM<K>],
                                            const float *bias, int cg, int lane, const WBuf &wb, uint32_t wl_off,
-                                           uint32_t wn_off, int wn_steps) {
+                                           uint32_t wn_off) {
   using X = XLive<K, MG_>;
   constexpr int NM = MM<K>;
   static_assert(KK32 % DEPTH == 0, "ring slot must be a compile-time function of k");
@@ -231,7 +231,7 @@ __device__ __forceinline__ void conv_layer(const char *src, char *dst, const Nbr
         bc[t][h] = lds_b128(src + off_cur[t][h]);
       }
     }
-#define TAP16(T) conv_tap<K, KK32, DEPTH, MG_, T>(src, nb, acc, bc, bn, off_cur, off_nxt, a, qoff, rb, wb, wl_off, wn_off, wn_steps)
+#define TAP16(T) conv_tap<K, KK32, DEPTH, MG_, T>(src, nb, acc, bc, bn, off_cur, off_nxt, a, qoff, rb, wb, wl_off, wn_off)
   TAP16(0); TAP16(1); TAP16(2); TAP16(3); TAP16(4); TAP16(5); TAP16(6); TAP16(7); TAP16(8);
 #undef TAP16
   epilogue<K, RESID>(acc, dst, bv, cg, MG_, q, rb);
@@ -344,15 +344,14 @@ __device__ __forceinline__ void tile(char *smem, const __bf16 *planes, int batch
   const uint32_t ct0_off = (uint32_t)(STEM + (size_t)(NM * cg_u) * LSTEPS * 64) * 16u;
   for (int L = 0; L < n_convs; ++L) {
     const uint32_t wl_off = ct0_off + (uint32_t)((size_t)L * LAYER * 16u);
-    const uint32_t wn_off = (kRingAlways && L + 1 == n_convs) ? wl_off : wl_off + (uint32_t)(LAYER * 16u);
-    const int wn_steps = L + 1 < n_convs ? LSTEPS : 0;
+    const uint32_t wn_off = L + 1 == n_convs ? wl_off : wl_off + (uint32_t)(LAYER * 16u);
     const bool even = (L & 1) == 0;
     if (K::MG == 1 || wave / K::CG == 0) {
-      if (even) conv_layer<K, KK32, DEPTH, false, 0>(X, Y, nb, ring, b, cg, lane, wb, wl_off, wn_off, wn_steps);
-      else conv_layer<K, KK32, DEPTH, true, 0>(Y, X, nb, ring, b, cg, lane, wb, wl_off, wn_off, wn_steps);
+      if (even) conv_layer<K, KK32, DEPTH, false, 0>(X, Y, nb, ring, b, cg, lane, wb, wl_off, wn_off);
+      else conv_layer<K, KK32, DEPTH, true, 0>(Y, X, nb, ring, b, cg, lane, wb, wl_off, wn_off);
     } else if constexpr (K::MG == 2) {
-      if (even) conv_layer<K, KK32, DEPTH, false, 1>(X, Y, nb, ring, b, cg, lane, wb, wl_off, wn_off, wn_steps);
-      else conv_layer<K, KK32, DEPTH, true, 1>(Y, X, nb, ring, b, cg, lane, wb, wl_off, wn_off, wn_steps);
+      if (even) conv_layer<K, KK32, DEPTH, false, 1>(X, Y, nb, ring, b, cg, lane, wb, wl_off, wn_off);
+      else conv_layer<K, KK32, DEPTH, true, 1>(Y, X, nb, ring, b, cg, lane, wb, wl_off, wn_off);
     }
     b += K::C;
     __syncthreads();

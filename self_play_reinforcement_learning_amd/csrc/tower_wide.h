@@ -3,7 +3,8 @@
 //
 // Included by tower.hip (namespace tower).  The trunk itself is tower_wide16.h; this file holds what it shares
 // with the plan it came from (round 3's 32x32x16 one-buffer trunk, removed after the 16x16x32 form replaced
-// it: DESIGN.md §4): the residual scratch (Scr, ScrBuf) and load_bias.
+// it: DESIGN.md §4): the residual scratch's size (Scr), its buffer-resource loads and stores (ScrBuf; the
+// offsets are tower_wide16.h's soff) and load_bias.
 //
 // Two ping-pong buffers of a 6-board tile at C = 256 would need 2 x 143.6 KB of LDS, so the two-buffer
 // kernel can run C = 256 only on 3-board, board-major tiles (128 rows): no edge-tile skipping (every tap of
@@ -25,9 +26,6 @@ template <class K>
 struct Scr {
   static constexpr size_t PER_WAVE = (size_t)K::MT * K::NT * 64 * 32;
   static constexpr size_t PER_WG = PER_WAVE * K::WAVES;
-  __device__ static uint4 *at(uint4 *base, int wave, int m, int t, int lane) {
-    return base + (((size_t)wave * K::MT + m) * K::NT + t) * 64 * 2 + lane * 2;
-  }
 };
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -45,9 +43,6 @@ struct ScrBuf {
   __amdgpu_buffer_rsrc_t rsrc;
   __device__ __forceinline__ explicit ScrBuf(uint4 *base) {
     rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)base, (short)0, (int)Scr<K>::PER_WG, 0x00020000);
-  }
-  __device__ static __forceinline__ int soff(int wave, int m, int t) {
-    return (int)(((size_t)wave * K::MT + m) * K::NT + t) * 64 * 32;
   }
   __device__ __forceinline__ uint4 load(int lane, int half, int so) const {
     return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 32 + half * 16, so, AUX));

@@ -92,8 +92,8 @@ __device__ __forceinline__ void epilogue(char *X, const f32x4 (&acc)[4][K::NT][2
 // cell tiles), then the in-place epilogue.
 template <class K, int DEPTH, bool RESID, bool SAVE>
 __device__ __forceinline__ void conv(char *X, const Nbr<K> &nb, bf16x8 (&a)[DEPTH][4], const float *bias, int wave,
-                                     int lane, const WBuf &wb, uint32_t wl_off, uint32_t wn_off, int wn_steps,
-                                     uint4 *scr, float *sbias) {
+                                     int lane, const WBuf &wb, uint32_t wl_off, uint32_t wn_off, uint4 *scr,
+                                     float *sbias) {
   using Xl = XLive<K, 0>;
   constexpr int KK32 = K::C / 32;
   static_assert(K::C == K::THREADS, "one bias value per thread");
@@ -121,7 +121,7 @@ __device__ __forceinline__ void conv(char *X, const Nbr<K> &nb, bf16x8 (&a)[DEPT
       }
     }
 #define TAPW16(T) \
-  m16::conv_tap<K, KK32, DEPTH, 0, T>(X, nb, acc, bc, bn, off_cur, off_nxt, a, qoff, rb, wb, wl_off, wn_off, wn_steps)
+  m16::conv_tap<K, KK32, DEPTH, 0, T>(X, nb, acc, bc, bn, off_cur, off_nxt, a, qoff, rb, wb, wl_off, wn_off)
   TAPW16(0); TAPW16(1); TAPW16(2); TAPW16(3); TAPW16(4); TAPW16(5); TAPW16(6); TAPW16(7); TAPW16(8);
 #undef TAPW16
   sbias[threadIdx.x] = bmine;
@@ -241,12 +241,11 @@ __device__ __forceinline__ void tile(char *smem, const __bf16 *planes, int batch
   // branch (66 spilled VGPRs, reloaded there)
   for (int L = 0; L < n_convs; L += 2) {
     const uint32_t wl_off = ct0_off + (uint32_t)((size_t)L * LAYER * 16u);
-    conv<K, DEPTH, false, false>(X, nb, ring, b, wave, lane, wb, wl_off, wl_off + (uint32_t)(LAYER * 16u), LSTEPS, scr,
-                                 sbias);
+    conv<K, DEPTH, false, false>(X, nb, ring, b, wave, lane, wb, wl_off, wl_off + (uint32_t)(LAYER * 16u), scr, sbias);
     b += K::C;
     const uint32_t wl1 = wl_off + (uint32_t)(LAYER * 16u);
-    const uint32_t wn1 = (kRingAlways && L + 2 == n_convs) ? wl1 : wl1 + (uint32_t)(LAYER * 16u);
-    conv<K, DEPTH, true, true>(X, nb, ring, b, wave, lane, wb, wl1, wn1, L + 2 < n_convs ? LSTEPS : 0, scr, sbias);
+    const uint32_t wn1 = L + 2 == n_convs ? wl1 : wl1 + (uint32_t)(LAYER * 16u);
+    conv<K, DEPTH, true, true>(X, nb, ring, b, wave, lane, wb, wl1, wn1, scr, sbias);
     b += K::C;
   }
   head_layer<K>(X, wblk + (size_t)n_convs * LAYER, b, out, board0, batch, wave, lane);

@@ -335,7 +335,7 @@ class HipTowerEvaluator(Evaluator):
         self.lo_w = t.linear_output.weight.detach().to(dev, bf)
         self.lo_b = t.linear_output.bias.detach().to(dev, bf)
         self.ff, self.cells = ff, cells
-        # fused-heads blobs (csrc/tower.hip k_heads)
+        # fused-heads blobs (csrc/tower_heads.h k_heads)
         K = cells * ff
         wp = torch.zeros(32, K, dtype=bf, device=dev)
         wp[: self.A] = self.lp_w

@@ -5,7 +5,7 @@ interactive play on the host envs (`__call__(s) -> action`, `reset(player)`,
 `play_action(action, player)`).  Passed as the `policy_gen` of an
 `evaluation_policy_container`, they make `SelfPlayScheduler.compare_models` /
 evaluation games run them ON THE DEVICE as arena players
-(`SPMCTS_PLAYER_LOOKAHEAD` / `SPMCTS_PLAYER_RANDOM`, csrc/spmcts.hip
+(`SPMCTS_PLAYER_LOOKAHEAD` / `SPMCTS_PLAYER_RANDOM`, csrc/arena_games.h
 `hardcoded_move`) against the policy's trees.
 """
 import random

@@ -84,9 +84,10 @@ def test_tower_rows_independent_of_batch(dtype, ff):
 @pytest.mark.parametrize("n", [1, 37, 700, 1536, 2336, 4000])
 @pytest.mark.parametrize("ff", [32, 64])
 def test_forward_dev_matches_host_count(n, dtype, ff):
-    """The device-count launch (row count read on device, full/middle/half workgroups chosen on
-    device) gives the host-count results bit for bit on the live rows.  On 256 CUs, 2,336 and 4,000
-    rows leave tails of 800 and 928 boards: one round of the 4-board middle tile."""
+    """The device-count launch (row count read on device, each workgroup's boards chosen on device)
+    gives the host-count results bit for bit on the live rows.  On 256 CUs, 2,336 and 4,000 rows
+    leave tails of 800 and 928 boards after the whole rounds: both 7x6 tile sets have 6-board tiles
+    only, so a tail is one more round of them, the last tile partly empty."""
     W, H, A = 7, 6, 7
     net = _net(W, H, A, 2, ff)
     max_rows = 4096

@@ -153,14 +153,14 @@ def test_product_library_holds_only_the_shipped_trunk_kernels():
     dyn = [n for n in names if n.startswith("_ZN5tower11k_tower_dyn")]
     host = [n for n in names if n.startswith("_ZN5tower7k_tower")]
     assert len(dyn) == 8 and len(host) == 8, (len(dyn), len(host))
-    # the 7x6 C = 128 kernels: Cfg<128, 256, 7, 6, ..., M16 = true> only (mangled ...Lb0ELb1EE: ONEBUF, M16)
+    # the 7x6 C = 128 kernels: tower.hip's Tiles7x6c128 (256 rows, M16) only (mangled ...Lb0ELb1EE: ONEBUF, M16)
     c128 = [n for n in dyn + host if "CfgILi128ELi256ELi7ELi6E" in n]
     assert len(c128) == 4 and all("Lb0ELb1EE" in n for n in c128), c128
     assert not [n for n in dyn + host if "CfgILi128ELi192ELi7ELi6E" in n or "CfgILi128ELi128ELi7ELi6E" in n]
-    # the 7x6 C = 256 kernels: Cfg<256, 256, 7, 6, ..., ONEBUF = true, M16 = true> only
+    # the 7x6 C = 256 kernels: tower.hip's Tiles7x6c256 (256 rows, ONEBUF, M16) only
     c256 = [n for n in dyn + host if "CfgILi256ELi" in n and "ELi7ELi6E" in n]
     assert len(c256) == 4 and all("CfgILi256ELi256ELi7ELi6E" in n and "Lb1ELb1EE" in n for n in c256), c256
-    # Cfg<C, ROWS, W, H, CG, WAVES, ...>
+    # Cfg's leading parameters: C, ROWS, W, H, CG, WAVES
     cfgs = re.findall(r"(?:CfgI|NS1_I)Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", " ".join(dyn + host))
     assert cfgs
     assert {(c[0], c[2], c[3]) for c in cfgs} == {("128", "7", "6"), ("256", "7", "6"), ("128", "3", "3"),
