@@ -33,8 +33,10 @@ __device__ __forceinline__ uint32_t leaf_hash(uint64_t a, uint64_t b) {
 
 template <class G>
 __global__ __launch_bounds__(256) void k_dedup_insert(View v) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= v.NS || !v.need[t]) return;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= v.dn * v.K) return;
+  const int t = dom_slot(v, c);
+  if (t < 0 || !v.need[t]) return;
   uint64_t own, opp;
   leaf_key<G>(v, t, own, opp);
   const unsigned long long mine = ((unsigned long long)v.dgen << 32) | (uint32_t)t;
@@ -64,8 +66,9 @@ __global__ __launch_bounds__(256) void k_dedup_insert(View v) {
   set_err(v, SPMCTS_ERR_STATE);  // unreachable: the table has >= 2 NS entries
 }
 
-// owner flags, one independent load pair per slot (the scan below then reads one byte per slot
-// instead of a dependent dent -> dtab chain per slot in its serial chunk loop); a leader lane also
+// owner flags, one independent load pair per slot, and the row flag of each compact index of the launch
+// domain (crow: the scan below then reads consecutive words instead of a dependent dent -> dtab chain per
+// slot in its serial chunk loop; without dedup every pending slot owns its row); a leader lane also
 // keeps each owner's key for its followers' lookups this step (okey: nothing else writes it until its
 // next step's k_dedup_owner, which runs after every follower's lookup of this step)
 // Evaluation cache (spmcts_set_eval_cache): linear probing over at most CACHE_PROBES entries from the key's
@@ -139,16 +142,24 @@ __device__ __forceinline__ bool cache_hit(const View &v, int t) {
 
 template <class G>
 __global__ __launch_bounds__(256) void k_dedup_owner(View v) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= v.NS) return;
-  const bool own = v.need[t] && (int)(uint32_t)v.dtab[v.dent[t]] == t;
-  v.down[t] = own ? (v.cwin && cache_hit<G>(v, t) ? 3 : 1) : 0;
-  if (own && v.lead) {
-    uint64_t a, b;
-    leaf_key<G>(v, t, a, b);
-    v.okey[2 * (size_t)t] = a;
-    v.okey[2 * (size_t)t + 1] = b;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= v.dn * v.K) return;
+  const int t = dom_slot(v, c);
+  int d = 0;
+  if (t >= 0 && !v.dedup) {
+    d = v.need[t] != 0;  // no dedup: every pending leaf owns its row
+  } else if (t >= 0) {
+    const bool own = v.need[t] && (int)(uint32_t)v.dtab[v.dent[t]] == t;
+    d = own ? (v.cwin && cache_hit<G>(v, t) ? 3 : 1) : 0;
+    v.down[t] = (uint8_t)d;
+    if (own && v.lead) {
+      uint64_t a, b;
+      leaf_key<G>(v, t, a, b);
+      v.okey[2 * (size_t)t] = a;
+      v.okey[2 * (size_t)t + 1] = b;
+    }
   }
+  v.crow[c] = d ? t * 4 + d : 0;
 }
 
 // Follower lane (spmcts_set_leaf_peer), a simulation step: owner flags as k_dedup_owner, and each owner
@@ -160,14 +171,20 @@ __global__ __launch_bounds__(256) void k_dedup_owner(View v) {
 template <class G>
 __global__ __launch_bounds__(256) void k_dedup_owner_peer(View v, const uint64_t *ptab, const uint64_t *pkey,
                                                           const uint8_t *pdown, int pmask, uint32_t pgen) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= v.NS) return;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= v.dn * v.K) return;
+  const int t = dom_slot(v, c);
+  if (t < 0) {
+    v.crow[c] = 0;
+    return;
+  }
   int d = 0, xp = -1;
   if (v.need[t] && (int)(uint32_t)v.dtab[v.dent[t]] == t) {
     d = 1;
     if (v.cwin && cache_hit<G>(v, t)) {  // the follower's own cache first: no wait on the leader's outputs
       v.down[t] = 3;
       v.xpeer[t] = -1;
+      v.crow[c] = t * 4 + 3;
       return;
     }
     uint64_t own, opp;
@@ -189,14 +206,17 @@ __global__ __launch_bounds__(256) void k_dedup_owner_peer(View v, const uint64_t
   }
   v.down[t] = (uint8_t)d;
   v.xpeer[t] = xp;
+  v.crow[c] = d ? t * 4 + d : 0;
 }
 
 // the leader's outputs of this step into the follower's rows of the slots it serves (down 2), on the
 // leader's stream after its heads (spmcts_peer_push): probs [row][A] f32, values [row] f32
 __global__ __launch_bounds__(256) void k_peer_push(View v, const int32_t *psrow, const float *pprobs,
                                                    const float *pvalues, float *probs, float *values) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= v.NS || v.down[t] != 2) return;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= v.dn * v.K) return;
+  const int t = dom_slot(v, c);
+  if (t < 0 || v.down[t] != 2) return;
   const int r1 = v.srow[t], r0 = psrow[v.xpeer[t]];
   for (int a = 0; a < v.A; ++a) probs[(size_t)r1 * v.A + a] = pprobs[(size_t)r0 * v.A + a];
   values[r1] = pvalues[r0];
@@ -210,8 +230,10 @@ __global__ __launch_bounds__(256) void k_peer_push(View v, const int32_t *psrow,
 template <class G>
 __global__ __launch_bounds__(256) void k_cache_io(View v, float *probs0, float *values0, float *probs1,
                                                   float *values1) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= v.NS || !v.need[t]) return;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= v.dn * v.K) return;
+  const int t = dom_slot(v, c);
+  if (t < 0 || !v.need[t]) return;
   const int d = v.down[t];
   if (d == 0) return;
   const int A = v.A;
@@ -252,12 +274,12 @@ __global__ __launch_bounds__(256) void k_cache_io(View v, float *probs0, float *
   }
 }
 
-__device__ __forceinline__ bool row_owner(const View &v, int t) { return v.dedup ? v.down[t] == 1 : v.need[t] != 0; }
-
 // duplicates read their owner's row
 __global__ __launch_bounds__(256) void k_dedup_alias(View v) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= v.NS || !v.need[t]) return;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= v.dn * v.K) return;
+  const int t = dom_slot(v, c);
+  if (t < 0 || !v.need[t]) return;
   const int s = (int)(uint32_t)v.dtab[v.dent[t]];
   if (s != t) v.srow[t] = v.srow[s];
 }
@@ -268,6 +290,32 @@ __global__ __launch_bounds__(256) void k_dedup_alias(View v) {
 // in the bench trace, profiles/r04_bench_prof/; 256 threads: 64 us, two rounds of flag loads per pass)
 constexpr int SCAN_THREADS = 512;
 constexpr int SCAN_WAVES = SCAN_THREADS / 64;
+constexpr int SCAN_BATCH = 20;  // words of crow past its NS entries (a batch is loaded whole, then masked)
+
+// One thread's chunk [lo, hi) of the step's row flags (View::crow, the domain's compact order): f(slot, d, n1)
+// for each slot with a row, in order.  d: 1 = a row its network evaluates, 2 / 3 = a served row (leader /
+// cache); n1: a network-1 tree's slot.  SCAN_BATCH flags at a time, one round of independent loads of
+// consecutive words (and one of the trees' networks in a two-network arena): the bench's lanes have 16 or 17
+// slots per thread, one batch.
+template <class F>
+__device__ __forceinline__ void scan_chunk(const View &v, int lo, int hi, F &&f) {
+  for (int base = lo; base < hi; base += SCAN_BATCH) {
+    int e[SCAN_BATCH];
+    uint32_t n1 = 0;
+#pragma unroll
+    for (int u = 0; u < SCAN_BATCH; ++u) e[u] = v.crow[base + u];
+#pragma unroll
+    for (int u = 0; u < SCAN_BATCH; ++u)
+      if (base + u >= hi) e[u] = 0;
+    if (v.seg1 < v.NS) {  // two-network arena (single-network: no tnet loads)
+#pragma unroll
+      for (int u = 0; u < SCAN_BATCH; ++u) n1 |= (v.tnet[(e[u] >> 2) / v.K] ? 1u : 0u) << u;
+    }
+#pragma unroll
+    for (int u = 0; u < SCAN_BATCH; ++u)
+      if (e[u]) f(e[u] >> 2, e[u] & 3, ((n1 >> u) & 1u) != 0);
+  }
+}
 
 __global__ __launch_bounds__(SCAN_THREADS) void k_scan_need(View v, int32_t *count_out) {
   // wave totals of the two segments' owner counts (a two-level scan: 6 shuffle steps within each wave,
@@ -275,32 +323,21 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_need(View v, int32_t *cou
   // and 8 KB of LDS)
   __shared__ int32_t s_w0[SCAN_WAVES], s_w1[SCAN_WAVES], s_w2[SCAN_WAVES], s_w4[SCAN_WAVES];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int T = v.NS;  // pending slots (tree * K + j), tree order then in-flight order
+  // the domain's pending slots in compact order (list entry, then in-flight index): slot order, as the list
+  // ascends; each thread a contiguous chunk of them
+  const int T = v.dn * v.K;
   const int chunk = (T + SCAN_THREADS - 1) / SCAN_THREADS;
   const int lo = min(T, tid * chunk), hi = min(T, lo + chunk);
   // c0 / c1: network-0 / network-1 rows the networks evaluate; c2 / c4: served rows (leader- or cache-served) of
   // network 0 / 1, numbered after the evaluated rows of their segment; c3: cache-served rows (a counter)
   int c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;
-  const bool two = v.seg1 < v.NS;  // two-network arena (single-network: no tnet loads)
-  // unrolled so each thread's chunk of flags is fetched in one round of independent loads
-  if (v.served) {
-#pragma unroll 16
-    for (int t = lo; t < hi; ++t) {
-      const int d = v.down[t];
-      const bool n1 = two && v.tnet[t / v.K] != 0;
-      c0 += d == 1 && !n1;
-      c1 += d == 1 && n1;
-      c2 += d >= 2 && !n1;
-      c4 += d >= 2 && n1;
-      c3 += d == 3;
-    }
-  } else {
-#pragma unroll 16
-    for (int t = lo; t < hi; ++t)
-      if (row_owner(v, t)) {
-        if (v.tnet[t / v.K]) ++c1; else ++c0;
-      }
-  }
+  scan_chunk(v, lo, hi, [&](int, int d, bool n1) {
+    c0 += d == 1 && !n1;
+    c1 += d == 1 && n1;
+    c2 += d >= 2 && !n1;
+    c4 += d >= 2 && n1;
+    c3 += d == 3;
+  });
   // inclusive scans of (c0, c1, c2, c4) in thread order: within the wave, then over the wave totals
   int i0 = c0, i1 = c1, i2 = c2, i4 = c4;
 #pragma unroll
@@ -347,36 +384,22 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_need(View v, int32_t *cou
   i1 += wave ? s_w1[wave - 1] : 0;
   i2 += wave ? s_w2[wave - 1] : 0;
   i4 += wave ? s_w4[wave - 1] : 0;
+  // served rows follow all evaluated rows of their network's segment
   int r0 = i0 - c0, r1 = v.seg1 + i1 - c1;
-  if (v.served) {
-    // served rows follow all evaluated rows of their network's segment
-    int r2 = s_w0[SCAN_WAVES - 1] + i2 - c2, r4 = v.seg1 + s_w1[SCAN_WAVES - 1] + i4 - c4;
-#pragma unroll 16
-    for (int t = lo; t < hi; ++t) {
-      const int d = v.down[t];
-      if (d == 0) continue;
-      const bool n1 = two && v.tnet[t / v.K] != 0;
-      if (d == 1) {
-        const int r = n1 ? r1++ : r0++;
-        v.row_tree[r] = t;
-        v.srow[t] = r;
-      } else {
-        v.srow[t] = n1 ? r4++ : r2++;
-      }
+  int r2 = s_w0[SCAN_WAVES - 1] + i2 - c2, r4 = v.seg1 + s_w1[SCAN_WAVES - 1] + i4 - c4;
+  scan_chunk(v, lo, hi, [&](int t, int d, bool n1) {
+    if (d == 1) {
+      const int r = n1 ? r1++ : r0++;
+      v.row_tree[r] = t;
+      if (v.K > 1) v.srow[t] = r;
+    } else {
+      v.srow[t] = n1 ? r4++ : r2++;
     }
-    if (v.cwin) {  // cache-served rows (counters.cache_rows)
+  });
+  if (v.cwin) {  // cache-served rows (counters.cache_rows)
 #pragma unroll
-      for (int off = 32; off > 0; off >>= 1) c3 += __shfl_xor(c3, off, 64);
-      if (lane == 0 && c3) atomicAdd((unsigned long long *)&v.gcnt[11], (unsigned long long)c3);
-    }
-  } else {
-#pragma unroll 16
-    for (int t = lo; t < hi; ++t)
-      if (row_owner(v, t)) {
-        const int r = v.tnet[t / v.K] ? r1++ : r0++;
-        v.row_tree[r] = t;
-        if (v.K > 1) v.srow[t] = r;
-      }
+    for (int off = 32; off > 0; off >>= 1) c3 += __shfl_xor(c3, off, 64);
+    if (lane == 0 && c3) atomicAdd((unsigned long long *)&v.gcnt[11], (unsigned long long)c3);
   }
   if (tid == SCAN_THREADS - 1) {  // the last thread's inclusive prefix is each segment's total
     v.row_count[0] = i0;
@@ -400,9 +423,12 @@ __device__ __forceinline__ bool row_live(const View &v, int row) {
 template <class G>
 __global__ void k_encode(View v, void *out) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int row = (int)(gid / G::CELLS);
   const int cell = (int)(gid % G::CELLS);
-  if (row >= v.NS || !row_live(v, row)) return;
+  // the i-th live row: network 0's n0 rows from row 0, then network 1's n1 from row seg1 (n0 + n1 <= dn * K:
+  // a pending slot of the domain owns at most one row)
+  const int i = (int)(gid / G::CELLS), n0 = v.row_count[0];
+  if (i >= v.dn * v.K || i - n0 >= v.row_count[1]) return;
+  const int row = i < n0 ? i : v.seg1 + i - n0;
   const int t = v.row_tree[row];
   const int x = cell / G::H, y = cell % G::H;
   const uint64_t bit = 1ull << cell_bit<G>(x, y);

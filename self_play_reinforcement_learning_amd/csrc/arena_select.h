@@ -795,7 +795,8 @@ __device__ int fill_slot_vl(const View &v, int tree, int j, int limit, int &star
 // P-lane group each.  (LDS copies of the child blocks a tree's sims read, 16 per tree, were measured slower --
 // the isolated expand 250 -> 295-300 us, select unchanged: a launch starts with no copies, so most blocks are
 // copied once and read once, and the levels of a sim are a chain of short dependent LDS / permute / FP64
-// latencies, not memory round trips -- and removed, as were workgroups of 2..8 waves: DESIGN.md §4.)
+// latencies, not memory round trips -- and removed, as were workgroups of 2..8 waves for this kernel, once per
+// ply: DESIGN.md §4.  k_expand_vl, once per step, runs four waves per workgroup: EXPAND_THREADS.)
 template <class G>
 __global__ __launch_bounds__(64) void k_select_vl(View v, int n_active) {
   constexpr int P = G::APAD;

@@ -9,6 +9,10 @@ struct View {
   int T, cap, G, A;
   int iters;  // MCTreeSearch.iterations (bounds the last step of a K-in-flight search)
   int K, NS;  // simulations in flight per tree (virtual loss; 1 = sequential), pending slots = T * K
+  // launch domain of a step's per-slot kernels (by value per launch, launch_rows): the pending slots of dn
+  // trees -- every tree (dpack 0: entry i is tree i, dn = T) or the active list (dpack 1: entry i is tree
+  // active[i], -1 = none, dn = its length).  Slot ids stay global (tree * K + j): dom_tree / dom_slot below
+  int dn, dpack;
   double cpuct, x, alpha;
   int strong, evaluate, rng_mode, leaf_format, leaf_layout;
   // node store: one record of 32 * P bytes per child block (nd_* below)
@@ -43,6 +47,10 @@ struct View {
   int32_t *row_tree;  // row -> pending slot (tree * K + j)
   int32_t *srow;      // pending slot -> row (K > 1)
   int32_t *row_count;
+  // the step's row flags in the launch domain's compact order (k_dedup_owner[_peer] -> k_scan_need): entry c =
+  // slot * 4 + d for a slot with a row (d as `down` below: 1 a row its network evaluates, 2 / 3 a served row),
+  // else 0.  One contiguous word per slot of the domain, so each scan thread's chunk is one round of loads
+  int32_t *crow;
   // batch leaf dedup (K > 1, spmcts_set_leaf_dedup): pending leaves with the same network input share
   // one row.  dtab: open-addressing table of (generation << 32 | owner slot), dent: a slot's entry
   uint64_t *dtab;
@@ -56,7 +64,7 @@ struct View {
   uint64_t *okey;
   int32_t *xpeer;
   int lead;     // 1: this arena has followers (k_dedup_owner writes okey)
-  int peer_on;  // 1 in a follower's simulation-step launches (k_scan_need numbers down-2 slots after its own rows)
+  int peer_on;  // 1 in a follower's simulation-step launches (down-2 slots: rows after its own, k_scan_need)
   // evaluation cache (round 6, spmcts_set_eval_cache): network outputs of the arena's own rows kept for `cwin`
   // generations (one per ply / search), keyed like the dedup table; an owner slot whose key is there takes
   // the cached outputs (down 3, xc = the entry) in a row after the network rows, filled by k_cache_io.
@@ -67,7 +75,6 @@ struct View {
   int cwin, cmask;  // cwin 0 = off (also in launches where the cache is not live)
   uint32_t cgen;
   int cshared;  // 1: a follower lane using its leader's table (the leader inserts the rows it serves)
-  int served;  // 1: k_scan_need numbers down-2 / down-3 slots after the network rows (peer_on or the cache)
   float *root_prior;
   uint32_t *err;
   // games
@@ -159,3 +166,13 @@ template <class G>
 __device__ __forceinline__ size_t nbase(const View &v, int tree) {
   return (size_t)tree * (size_t)v.cap * G::APAD;
 }
+
+// The launch domain (View::dn, dpack): the tree of entry i < dn (-1: an empty list entry), and the pending
+// slot of compact index c < dn * K (entry c / K, in-flight index c % K; -1 for an empty entry).  Compact
+// order is slot order wherever the list ascends (the identity map; k_games_begin_ply's list).
+__device__ __forceinline__ int dom_tree(const View &v, int i) { return v.dpack ? v.active[i] : i; }
+__device__ __forceinline__ int dom_slot(const View &v, int c) {
+  const int i = c / v.K, tree = dom_tree(v, i);
+  return tree < 0 ? -1 : tree * v.K + (c - i * v.K);
+}
+

@@ -114,7 +114,18 @@ struct spmcts_arena {
   bool cache_step = false;
   bool cache_shared_step = false;  // that launch used the leader's table (cache_view)
   const uint64_t *cache_tab = nullptr;  // the table that launch looked its keys up in
+  // the packed launch domain (launch_rows): the active list is k_games_begin_ply's (ascending, one searching
+  // tree per game at most), and the last launch_rows ran over it; that step's spmcts_peer_push and
+  // spmcts_expand2 use the same domain
+  bool games_list = false;
+  bool packed_step = false;
 };
+
+// The launch domain of a step's per-slot kernels (View::dn, dpack): the active list, or every tree.
+static void set_domain(const spmcts_arena *h, View &v, bool packed) {
+  v.dn = packed ? h->n_active : v.T;
+  v.dpack = packed ? 1 : 0;
+}
 
 // The evaluation-cache table of a launch: a follower lane (spmcts_set_leaf_peer) whose leader runs a cache of
 // the same window, one generation apart at most, uses the leader's table -- one table for the GPU's lanes, so a
@@ -212,6 +223,7 @@ static void plan_arena(spmcts_arena *h, Plan &pl) {
   pl.add(&v.row_tree, NS);
   pl.add(&v.srow, NS);
   pl.add(&v.row_count, 4);
+  pl.add(&v.crow, NS + SCAN_BATCH);
   {
     size_t tab = 1;
     while (tab < 2 * NS) tab <<= 1;
@@ -285,6 +297,8 @@ static int setup_view(spmcts_arena *h, const spmcts_config *cfg) {
   if (v.K > P) return fail(-3, "search_threads must not exceed the lane group (8 for connect4, 16 for tictactoe)");
   v.iters = std::max(1, cfg->iterations);
   v.NS = v.T * v.K;
+  v.dn = v.T;  // full width (set_domain)
+  v.dpack = 0;
   v.seg1 = v.NS;
   v.record = 1;
   v.sim = 0;
@@ -430,7 +444,9 @@ int spmcts_peer_push(spmcts_arena *h, float *probs_dev, float *values_dev, const
   HIP_TRY(hipEventRecord(h->ev_lead, ls));
   HIP_TRY(hipStreamWaitEvent(h->push_stream, h->ev_lead, 0));
   HIP_TRY(hipStreamWaitEvent(h->push_stream, h->ev_rows, 0));
-  const int rc = launch(k_peer_push, h->v.NS, 256, h->push_stream, h->v, h->peer->v.srow, leader_probs_dev,
+  View v = h->v;
+  set_domain(h, v, h->packed_step);  // the domain whose k_dedup_owner_peer wrote this step's down / xpeer
+  const int rc = launch(k_peer_push, (long long)v.dn * v.K, 256, h->push_stream, v, h->peer->v.srow, leader_probs_dev,
                         leader_values_dev, probs_dev, values_dev);
   HIP_TRY(hipEventRecord(h->ev_push, h->push_stream));
   h->push_pending = true;
@@ -476,6 +492,7 @@ int spmcts_search_begin(spmcts_arena *h, const int32_t *trees_dev, int32_t n, sp
   if (!h) return fail(-1, "null arena");
   if (n > std::max(h->v.T, h->v.G)) return fail(-3, "too many active trees");
   h->n_active = n;
+  h->games_list = false;  // a caller's list: any order, so its steps launch at full width (launch_rows)
   h->v.sim = 0;
   if (h->v.cwin) ++h->v.cgen;  // a new evaluation-cache generation per search
   if (n <= 0) return 0;
@@ -490,46 +507,71 @@ static bool peer_live(const spmcts_arena *h) { return h->peer && h->v.dedup && h
 // `sim_step`: a simulation step's rows (spmcts_select / spmcts_leaf_rows), where a follower lane looks its
 // owner keys up in its leader's table; the end-of-ply expansions (spmcts_play_action, games_end_ply) stay
 // lane-local
+//
+// Launch domain.  A simulation step of a games-mode ply (the active list is k_games_begin_ply's) runs its
+// per-slot kernels -- dedup, scan, alias, encode here, then k_peer_push, k_cache_io and k_expand_vl
+// (spmcts_peer_push, spmcts_expand2) -- over the pending slots of the listed trees only: one tree per game
+// searches, so half of the T = 2 G trees' slots.  This rests on one invariant: in such a step no tree outside
+// the list has a pending slot (need set).  need is set in two places.  fill_slot_vl / k_select set it for the
+// tree they run on, and they run on listed trees only (k_select_vl, k_select: entries of `active`; k_expand_vl's
+// refill: a tree with started < limit, which draw_noise arms for listed trees alone, and which the domain
+// restricts to the list anyway).  set_node (k_games_end_ply, k_play_action) sets it for slot 0 of trees that do
+// not search, and the launch_rows that follows it is never a simulation step: it and its expand run at full
+// width and clear those slots before the next ply's list is written.  A listed tree's own slots are all
+// cleared by the last step's expand (every pending slot of a domain tree is completed there), so nothing
+// carries over when the other tree of the game searches next.  The list ascends (active[g] = 2 g + mover), so
+// compact order is slot order and k_scan_need numbers the same rows as at full width.  A caller's list
+// (spmcts_search_begin) may be in any order: those searches, and every end-of-ply launch, stay at full width.
+// Flags written per step (down, xpeer, xc, dent, srow) are written for the domain's slots only, so an idle
+// tree's slots keep those of its last search.  Every reader either tests need first (k_cache_io, k_dedup_alias,
+// k_expand_vl), runs on the writer's domain in the same step (k_peer_push: down, xpeer), or reads a leader's
+// slot found in the leader's table of this generation, which the leader's k_dedup_insert / k_dedup_owner wrote
+// this step (k_dedup_owner_peer: pdown, pkey).  k_scan_need reads no per-slot flag: the owner kernel of its
+// launch writes the row flag of every compact index of the domain (crow), empty entries included.  The
+// full-width passes rewrite down for every slot.
 static int launch_rows(spmcts_arena *h, void *leaves_dev, int32_t *leaf_count_dev, hipStream_t s, bool sim_step) {
   h->peer_step = false;
+  h->packed_step = sim_step && h->games_list;
   for (spmcts_arena *f : h->followers)  // a leader rewrites its table, keys and (later) outputs only after the pushes
     if (f->push_pending) {
       HIP_TRY(hipStreamWaitEvent(s, f->ev_push, 0));
       f->push_pending = false;
     }
   View v = h->v;
+  set_domain(h, v, h->packed_step);
+  const long long slots = (long long)v.dn * v.K;  // the domain's pending slots: one thread each
   v.peer_on = 0;
   // the evaluation cache is live in leaf-dedup launches (spmcts_set_eval_cache)
   h->cache_step = v.cwin > 0 && v.dedup;
   if (!h->cache_step) v.cwin = 0;
   h->cache_shared_step = h->cache_step && cache_view(h, v);
   h->cache_tab = h->cache_step ? v.crec : nullptr;
-  v.served = h->cache_step ? 1 : 0;
   if (v.dedup) {
     if (++h->v.dgen == 0) ++h->v.dgen;  // generation 0 = the zeroed table
     v.dgen = h->v.dgen;
     v.lead = h->followers.empty() ? 0 : 1;
-    TRY(LAUNCH(h, k_dedup_insert, v.NS, 256, s, v));
+    TRY(LAUNCH(h, k_dedup_insert, slots, 256, s, v));
     if (sim_step && peer_live(h)) {
       // the leader's table and keys of this step are complete (its ev_ins), and stay so until this step's
       // rows are numbered (the leader's stream waits for our ev_rows before it moves on: spmcts_peer_push)
       const spmcts_arena *p = h->peer;
       HIP_TRY(hipStreamWaitEvent(s, p->ev_ins, 0));
       v.peer_on = 1;
-      v.served = 1;
-      TRY(LAUNCH(h, k_dedup_owner_peer, v.NS, 256, s, v, p->v.dtab, p->v.okey, p->v.down, p->v.dmask, p->v.dgen));
+      TRY(LAUNCH(h, k_dedup_owner_peer, slots, 256, s, v, p->v.dtab, p->v.okey, p->v.down, p->v.dmask, p->v.dgen));
     } else {
-      TRY(LAUNCH(h, k_dedup_owner, v.NS, 256, s, v));
+      TRY(LAUNCH(h, k_dedup_owner, slots, 256, s, v));
     }
     if (v.lead) HIP_TRY(hipEventRecord(h->ev_ins, s));
+  } else {
+    TRY(LAUNCH(h, k_dedup_owner, slots, 256, s, v));  // no dedup: every pending slot's row flag (crow)
   }
   TRY(launch(k_scan_need, SCAN_THREADS, SCAN_THREADS, s, v, leaf_count_dev));  // one block
-  if (v.dedup) TRY(launch(k_dedup_alias, v.NS, 256, s, v));
+  if (v.dedup) TRY(launch(k_dedup_alias, slots, 256, s, v));
   if (v.peer_on) {
     HIP_TRY(hipEventRecord(h->ev_rows, s));
     h->peer_step = true;  // spmcts_peer_push brings the leader's outputs before the expand
   }
-  if (leaves_dev) TRY(LAUNCH(h, k_encode, (long long)v.NS * h->cells, 256, s, v, leaves_dev));
+  if (leaves_dev) TRY(LAUNCH(h, k_encode, slots * h->cells, 256, s, v, leaves_dev));
   return 0;
 }
 
@@ -563,17 +605,20 @@ int spmcts_expand2(spmcts_arena *h, const float *probs0_dev, const float *values
   if (h->peer_step) return fail(-4, "a follower lane's simulation step needs spmcts_peer_push before its expand");
   if (h->v.seg1 < h->v.NS && (!probs1_dev || !values1_dev))
     return fail(-1, "two-network arena needs network-1 outputs");
+  View dv = h->v;  // the domain of the step's rows (launch_rows)
+  set_domain(h, dv, h->packed_step);
   if (h->cache_step) {  // the rows of this step consulted the evaluation cache: fills and inserts first
-    View v = h->v;
+    View v = dv;
     if (h->cache_shared_step) cache_view(h, v);
     if (v.crec != h->cache_tab) return fail(-4, "the evaluation cache table changed between a step's rows and its expand");
-    TRY(LAUNCH(h, k_cache_io, h->v.NS, 256, (hipStream_t)stream, v, (float *)probs0_dev, (float *)values0_dev,
-               (float *)probs1_dev, (float *)values1_dev));
+    TRY(LAUNCH(h, k_cache_io, (long long)v.dn * v.K, 256, (hipStream_t)stream, v, (float *)probs0_dev,
+               (float *)values0_dev, (float *)probs1_dev, (float *)values1_dev));
     h->cache_step = false;
   }
-  const long long lanes = (long long)h->v.T * h->P;  // one P-lane group per tree
-  if (h->v.K > 1)
-    return LAUNCH(h, k_expand_vl, lanes, 64, (hipStream_t)stream, h->v, probs0_dev, values0_dev, probs1_dev, values1_dev);
+  if (h->v.K > 1)  // one P-lane group per tree of the domain
+    return LAUNCH(h, k_expand_vl, (long long)dv.dn * h->P, EXPAND_THREADS, (hipStream_t)stream, dv, probs0_dev,
+                  values0_dev, probs1_dev, values1_dev);
+  const long long lanes = (long long)h->v.T * h->P;  // one P-lane group per row
   return LAUNCH(h, k_expand, lanes, 64, (hipStream_t)stream, h->v, probs0_dev, values0_dev, probs1_dev, values1_dev);
 }
 
@@ -799,6 +844,7 @@ int spmcts_games_begin_ply(spmcts_arena *h, spmcts_stream stream) {
   if (!h) return fail(-1, "null arena");
   if (h->v.G <= 0) return fail(-4, "arena has no game slots");
   h->n_active = h->v.G;
+  h->games_list = true;  // active[g] = the searching tree of game g, or -1: ascending
   h->v.sim = 0;
   if (h->v.cwin) ++h->v.cgen;  // a new evaluation-cache generation per ply
   TRY(LAUNCH(h, k_games_begin_ply, h->v.G, 128, (hipStream_t)stream, h->v));
