@@ -301,7 +301,7 @@ int spmcts_table_net(int32_t game, int32_t width, int32_t height, const void *le
  * inference_worker.py:117) MFMA with fp32 accumulation.  planes_dev: bf16 [batch][W][H][3]
  * (NHWC leaf rows, 0/1 planes); weights and features_dev [batch][W*H][channels/2] (policy |
  * value head channels, cell-major) in the flags' element type.  Packed weight/bias layout:
- * csrc/tower.hip.  Instantiated for 7x6 and 3x3 boards with channels 128 or 256. */
+ * csrc/tower_kernels.h (the M16 layout's block convs: csrc/tower_m16.h).  Instantiated for 7x6 and 3x3 boards with channels 128 or 256. */
 #define SPMCTS_TOWER_F16 2
 int spmcts_tower_forward(int32_t width, int32_t height, int32_t channels, int32_t n_blocks, const void *planes_dev,
                          int32_t batch, const void *weights_dev, const float *bias_dev, void *features_dev,

@@ -1,4 +1,4 @@
-"""Edge-tile row layout of a 6-board Connect4 tile (tower.hip Cfg::EDGE), conflict-free by construction.
+"""Edge-tile row layout of a 6-board Connect4 tile (tower_common.h Cfg::EDGE), conflict-free by construction.
 
 Writes self_play_reinforcement_learning_amd/csrc/tower_edge.h: EDGE_ROW (row -> board/x/y, 255 =
 padding), EDGE_CELL_ROW (cell -> row) and EDGE_NBR ([tap][row] -> source row, zero rows off the board).

@@ -1,7 +1,8 @@
 // tower_m16.h — the C = 128 Connect4 trunk on v_mfma_f32_16x16x32_{bf16,f16} (round 4).
 //
-// Included by tower.hip (namespace tower): uses Cfg (M16), Nbr, XLive, WBuf, lds_b128,
-// stem_layer's k-loop shape and head_layer from there.
+// Included by tower_kernels.h and tower_wide16.h (which shares lane_row, src_row, conv_tap and stem_store).  Uses
+// Cfg (M16), Ty, Nbr, XLive, WBuf, lds_b128, acc_init and head_layer from tower_common.h; its stem is the k-loop
+// of b32::stem_layer (tower_b32.h) with the phys16 store.
 //
 // The same workgroup plan as the 32x32x16 edge-tile trunk (6 boards in 256 edge-ordered rows, two LDS
 // buffers, 4 waves = 2 channel halves x 2 row halves, 12 of the 72 (tile, tap) pairs skipped), with each
@@ -20,7 +21,10 @@
 // (two 16x16x32 per 32x32x16, same loads) ran 1.88 vs 1.72 GHz and 5 % faster (profiles/r04/mfma_shape/).
 // Every tile of a launch is a 6-board tile (a batch tail takes one partly empty tile), so every board of
 // a batch goes through the same arithmetic: outputs stay batch-independent bit for bit.
+#pragma once
+#include "tower_common.h"
 
+namespace tower {
 namespace m16 {
 
 // 16-channel output tiles per wave: 4 with the C = 128 trunk's 2 x 2 wave plan (channel halves x row halves) and
@@ -59,15 +63,6 @@ __device__ __forceinline__ int lane_row(int n) {
 template <class K>
 __device__ __forceinline__ int src_row(const Nbr<K> &nb, int mg, int t, int h, int rb, int tap) {
   return (int)nb.tab[tap * K::ROWS + (mg * K::NT + t) * 32 + rb + h];
-}
-
-template <class K>
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  if constexpr (K::BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
-                                                  0);
 }
 
 // One tap of a layer: KK32 k-steps of 32 input channels; B fragments one k-step ahead (the next tap's
@@ -122,7 +117,7 @@ __device__ __forceinline__ void conv_tap(const char *src, const Nbr<K> &nb, f32x
     if (sn < STEPS) {
 #pragma unroll
       for (int mm = 0; mm < NM; ++mm) a[slot][mm] = wb.load(wl_off + mm * MSTRIDE + (uint32_t)sn * 1024u);
-    } else {  // unconditional, the last layer included (see conv_layer in tower.hip)
+    } else {  // unconditional, the last layer included (see b32::conv_layer, tower_b32.h)
 #pragma unroll
       for (int mm = 0; mm < NM; ++mm) a[slot][mm] = wb.load(wn_off + mm * MSTRIDE + (uint32_t)(sn - STEPS) * 1024u);
     }
@@ -133,7 +128,7 @@ __device__ __forceinline__ void conv_tap(const char *src, const Nbr<K> &nb, f32x
 #pragma unroll
         for (int mm = 0; mm < NM; ++mm)
           if ((LV >> t) & 1u)
-            acc[mm][t][h] = mfma16<K>(acur[mm], bc[t][h], (TAP == 0 && k == 0) ? f32x4{} : acc[mm][t][h]);
+            acc[mm][t][h] = K::mfma16(acur[mm], bc[t][h], (TAP == 0 && k == 0) ? f32x4{} : acc[mm][t][h]);
     // one operand read or weight load per MFMA gap: 2 NTA LDS reads and NM weight loads among 2 NM NTA MFMAs
 #pragma unroll
     for (int i = 0; i < 2 * NTA; ++i) {
@@ -265,7 +260,7 @@ __device__ __forceinline__ void stem(const char *src, char *dst, const Nbr<K> &n
                                      int wave, int lane) {
   const int h = lane >> 5;
   f32x16 acc[K::MT][K::NT];
-  acc_init<K, false>(acc, dst, bias, wave, lane);
+  acc_init<K>(acc, bias, wave, lane);
   bf16x8 a[9][K::MT];
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap)
@@ -283,14 +278,13 @@ __device__ __forceinline__ void stem(const char *src, char *dst, const Nbr<K> &n
   stem_store<K>(acc, dst, wave, lane);
 }
 
-// One workgroup's tile (the two-buffer edge layout of tower_tile): stem (32x32x16) -> 2 n_blocks convs
+// One workgroup's tile (two buffers, the edge layout): stem (32x32x16) -> 2 n_blocks convs
 // (16x16x32) -> head convs (head_layer, 32x32x16 over the phys16 channel order).
 template <class K>
 __device__ __forceinline__ void tile(char *smem, const __bf16 *planes, int batch, int board0, int n_blocks,
                                      const bf16x8 *wpk, const float *bias, uint16_t *out) {
-  static_assert(K::EDGE && K::C == 128 && K::WAVES == 4 && !K::ONEBUF &&
-                    ((K::CG == 2 && K::MG == 2) || (K::CG == 4 && K::MG == 1)),
-                "m16 trunk: C = 128 edge tiles, 2 channel halves x 2 row halves (or 4 channel quarters x 1)");
+  static_assert(K::EDGE && K::C == 128 && K::WAVES == 4 && !K::ONEBUF && K::CG == 2 && K::MG == 2,
+                "m16 trunk: C = 128 edge tiles, 2 channel halves x 2 row halves");
   constexpr int NM = MM<K>;
   char *X = smem;
   char *Y = smem + K::BUF;
@@ -346,10 +340,10 @@ __device__ __forceinline__ void tile(char *smem, const __bf16 *planes, int batch
     const uint32_t wl_off = ct0_off + (uint32_t)((size_t)L * LAYER * 16u);
     const uint32_t wn_off = L + 1 == n_convs ? wl_off : wl_off + (uint32_t)(LAYER * 16u);
     const bool even = (L & 1) == 0;
-    if (K::MG == 1 || wave / K::CG == 0) {
+    if (wave / K::CG == 0) {
       if (even) conv_layer<K, KK32, DEPTH, false, 0>(X, Y, nb, ring, b, cg, lane, wb, wl_off, wn_off);
       else conv_layer<K, KK32, DEPTH, true, 0>(Y, X, nb, ring, b, cg, lane, wb, wl_off, wn_off);
-    } else if constexpr (K::MG == 2) {
+    } else {
       if (even) conv_layer<K, KK32, DEPTH, false, 1>(X, Y, nb, ring, b, cg, lane, wb, wl_off, wn_off);
       else conv_layer<K, KK32, DEPTH, true, 1>(Y, X, nb, ring, b, cg, lane, wb, wl_off, wn_off);
     }
@@ -360,3 +354,4 @@ __device__ __forceinline__ void tile(char *smem, const __bf16 *planes, int batch
 }
 
 }  // namespace m16
+}  // namespace tower

@@ -1,26 +1,79 @@
 // tower_wide16.h — the C = 256 one-buffer trunk on v_mfma_f32_16x16x32_{bf16,f16} (round 5).
 //
-// Included by tower.hip (namespace tower) after tower_wide.h and tower_m16.h: the workgroup plan of
-// tower_wide.h (6 boards in 256 edge-ordered rows, ONE activation buffer, the block input kept in a
-// per-workgroup global scratch for the residual, 4 waves = 4 channel quarters x all 8 cell tiles, in-place
-// epilogues between barriers) with the k-loop of tower_m16.h (each 32-row x 32-channel output tile as
-// 2 x 2 tiles of 16 x 16 over K = 32 input channels, operand rows by lane_row, the phys16 channel order).
+// Included by tower_kernels.h; tower.hip sizes the residual scratch by Scr.  Uses Cfg (ONEBUF, M16), Ty, Nbr,
+// XLive, WBuf, lds_b128 and head_layer from tower_common.h, and lane_row, src_row, conv_tap and stem_store
+// from tower_m16.h.
+//
+// Two ping-pong buffers of a 6-board tile at C = 256 would need 2 x 143.6 KB of LDS, so a two-buffer kernel can
+// run C = 256 only on 3-board, board-major tiles (tower_b32.h on 128 rows: no edge-tile skipping, each weight
+// fragment serves 128 rows).  With ONE activation buffer the 6-board edge layout of the C = 128 trunk
+// (tower_edge.h) runs at C = 256:
+//   * 4 waves = 4 channel quarters x all 8 cell tiles.  A conv reads the buffer for all its k-steps with the
+//     k-loop of tower_m16.h (each 32-row x 32-channel output tile as 2 x 2 tiles of 16 x 16 over K = 32 input
+//     channels, operand rows by lane_row, the phys16 channel order; 12 of the 72 (tile, tap) pairs read zero
+//     padding only and are skipped), the waves meet at a barrier, then each wave writes its own output
+//     channels of all 256 rows in place, and a second barrier publishes them;
 //   * per wave: 4 16-channel tiles (64 output channels: one whole phys16 group, so a lane's 16 outputs of
 //     a cell are one contiguous 32-byte run) x 8 cell tiles x 2 row fragments = 64 f32x4 accumulators
-//     (the full AGPR file, as the 32x32x16 form's 16 f32x16);
-//   * the same FLOPs, LDS bytes and weight bytes per k-step as the 32x32x16 one-buffer trunk it replaced; a
-//     timing probe on that kernel (each 32x32x16 as two 16x16x32 on the same operands) ran the trunk 6.5 % faster at
-//     a 1.90 vs 1.80 GHz clock (profiles/r05/c256/shape_probe.txt);
-//   * residual scratch per workgroup: [wave][cell tile t][fragment h][64 lanes] x 32 bytes (the lane's run),
-//     the same 128 KB as tower_wide.h's, through the same buffer resource (stores at soffset 0).
+//     (the full AGPR file);
+//   * the residual of a block's second conv (the block input, overwritten by the first conv's outputs) goes
+//     through global memory: the stem and every second conv also store their outputs (the next block input,
+//     the same bf16 / fp16 bits as in LDS) to a per-workgroup scratch region (Scr, 128 KB), and the next
+//     second conv's epilogue reads them back, each lane its own 32-byte runs (the same lane and tile wrote
+//     them two layers earlier; coalesced 16-byte accesses);
+//   * the 16x16x32 MFMA holds a higher clock than the 32x32x16 one on the same operands: the trunk ran 6.5 %
+//     faster at 1.90 vs 1.80 GHz (profiles/r05/c256/shape_probe.txt).
 // Every tile of a launch is a 6-board tile (a batch tail takes one partly empty tile): every board goes
 // through the same arithmetic, so outputs are batch-independent bit for bit.  The weight blob is the M16
 // layout (evaluator._pack_conv_m16; spmcts_tower_weight_layout reports it for this shape).
+#pragma once
+#include "tower_common.h"
+#include "tower_m16.h"
 
+namespace tower {
 namespace wide16 {
 
 using m16::lane_row;
 using m16::src_row;
+
+// residual scratch per workgroup: [wave][cell tile t][fragment h][64 lanes] x 32 bytes (the lane's run; soff)
+template <class K>
+struct Scr {
+  static constexpr size_t PER_WG = (size_t)K::WAVES * K::NT * 2 * 64 * 32;
+};
+
+// Residual-scratch access through a buffer resource over this workgroup's region: the per-lane part of a
+// load's address is one 32-bit voffset (lane * 32 + half * 16) and the (wave, cell tile, fragment) part a
+// wave-uniform soffset, instead of 16 hoisted 64-bit addresses (the pointer form spilled 110 VGPRs on them).
+// Stores take the whole offset in the voffset and soffset = 0: hipcc (ROCm 7.2) inserts no wait state between
+// a buffer_store_dwordx4 whose soffset is an SGPR and a following VALU write of its data VGPRs (LLVM's
+// store-data hazard check exempts a register soffset), and on gfx950 that form stored wrong data -- every
+// C = 256 output differed (profiles/r04/c256_rsrc/probe_summary.txt: rsrc loads + pointer stores bit-equal,
+// pointer loads + SGPR-soffset rsrc stores not).  With soffset = 0 the hazard check applies.
+template <class K>
+struct ScrBuf {
+  static constexpr int AUX = 2;  // gfx950 CPol: nt, as the pointer form's nontemporal accesses
+  __amdgpu_buffer_rsrc_t rsrc;
+  __device__ __forceinline__ explicit ScrBuf(uint4 *base) {
+    rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)base, (short)0, (int)Scr<K>::PER_WG, 0x00020000);
+  }
+  __device__ __forceinline__ uint4 load(int lane, int half, int so) const {
+    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 32 + half * 16, so, AUX));
+  }
+  __device__ __forceinline__ void store(uint4 v, int lane, int half, int so) const {
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), rsrc, lane * 32 + half * 16 + so, 0, AUX);
+  }
+};
+
+// the stem's bias, per 32-channel tile m of the wave and accumulator group g
+template <class K>
+__device__ __forceinline__ void load_bias(float4 (&bv)[K::MT][4], const float *bias, int wave, int lane) {
+#pragma unroll
+  for (int m = 0; m < K::MT; ++m)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) bv[m][g] = *(const float4 *)(bias + (wave * K::MT + m) * 32 + 8 * g + 4 * (lane >> 5));
+}
 
 template <class K>
 __device__ __forceinline__ int soff(int wave, int t, int h) {
@@ -33,7 +86,7 @@ __device__ __forceinline__ int soff(int wave, int t, int h) {
 template <class K, bool RESID, bool SAVE>
 __device__ __forceinline__ void epilogue(char *X, const f32x4 (&acc)[4][K::NT][2], const float4 (&bv)[4], uint4 *scr,
                                          int wave, int q, int rb, int lane) {
-  const wide::ScrBuf<K> sb(scr);
+  const ScrBuf<K> sb(scr);
   const int wu = __builtin_amdgcn_readfirstlane(wave);
   const int ro = (64 * wave + 16 * q) * 2;  // the lane's run: channels 64 wave + 16 q .. + 16 (phys16)
   // residual reads two cell tiles at a time (32 registers in flight beside the 256 accumulator AGPRs)
@@ -141,7 +194,7 @@ __device__ __forceinline__ void stem(char *X, const Nbr<K> &nb, const bf16x8 *w,
   const int h = lane >> 5;
   f32x16 acc[K::MT][K::NT];
   float4 bv[K::MT][4];
-  wide::load_bias<K>(bv, bias, wave, lane);
+  load_bias<K>(bv, bias, wave, lane);
 #pragma unroll
   for (int m = 0; m < K::MT; ++m)
 #pragma unroll
@@ -170,7 +223,7 @@ __device__ __forceinline__ void stem(char *X, const Nbr<K> &nb, const bf16x8 *w,
   __syncthreads();  // every wave has read the stem input
   m16::stem_store<K>(acc, X, wave, lane);
   __syncthreads();
-  const wide::ScrBuf<K> sb(scr);
+  const ScrBuf<K> sb(scr);
   const int wu = __builtin_amdgcn_readfirstlane(wave);
   const int q = lane >> 4, rb = lane_row(lane & 15), ro = (64 * wave + 16 * q) * 2;
 #pragma unroll
@@ -185,13 +238,12 @@ __device__ __forceinline__ void stem(char *X, const Nbr<K> &nb, const bf16x8 *w,
 }
 
 // One workgroup's tile: boards [board0, board0 + BOARDS), all layers; scr = this workgroup's residual
-// scratch (wide::Scr<K>::PER_WG bytes).
+// scratch (Scr<K>::PER_WG bytes).
 template <class K>
 __device__ __forceinline__ void tile(char *smem, const __bf16 *planes, int batch, int board0, int n_blocks,
                                      const bf16x8 *wpk, const float *bias, uint16_t *out, uint4 *scr) {
   static_assert(K::EDGE && K::ONEBUF && K::M16 && K::MG == 1 && K::CG == 4 && K::WAVES == 4 && K::C == 256,
                 "wide16 trunk: C = 256 6-board edge tiles, one buffer, 4 channel quarters x all cell tiles");
-  static_assert(wide::Scr<K>::PER_WG == (size_t)K::WAVES * K::NT * 2 * 64 * 32, "scratch size");
   char *X = smem;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   Nbr<K> nb;
@@ -252,3 +304,4 @@ __device__ __forceinline__ void tile(char *smem, const __bf16 *planes, int batch
 }
 
 }  // namespace wide16
+}  // namespace tower

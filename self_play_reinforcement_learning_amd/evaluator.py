@@ -187,7 +187,7 @@ def make_evaluator(network, game, device=None, dtype=torch.bfloat16, leaf_layout
 # ----------------------------------------------------------------------------- fused HIP tower
 def phys_channel_order(c):
     """Logical channel held at each PHYSICAL LDS position of the fused tower's activations
-    (csrc/tower.hip phys_off): within every 32-channel tile, position 16h + 4g + j holds the MFMA
+    (csrc/tower_common.h phys_off): within every 32-channel tile, position 16h + 4g + j holds the MFMA
     output row 8g + 4h + j."""
     p = torch.arange(c)
     w = p % 32
@@ -217,7 +217,7 @@ def _pack_conv_m16(w, dtype=torch.bfloat16):
 
 
 def _pack_conv(w, cin_pad=None, in_perm=False, dtype=torch.bfloat16, order=None):
-    """[Cout][Cin][kh][kw] fp -> bf16 / fp16 fragments [Cout/32][taps][Cin/16][64 lanes][8] (csrc/tower.hip).
+    """[Cout][Cin][kh][kw] fp -> bf16 / fp16 fragments [Cout/32][taps][Cin/16][64 lanes][8] (csrc/tower_kernels.h).
     in_perm: the layer reads activations another tower layer wrote, which sit in the physical channel
     order (phys_channel_order), so the input-channel axis is permuted to match."""
     cout, cin, kh, kw = w.shape
@@ -234,7 +234,7 @@ def _pack_conv(w, cin_pad=None, in_perm=False, dtype=torch.bfloat16, order=None)
 
 
 class HipTowerEvaluator(Evaluator):
-    """ResidualTower leaf evaluation on the fused HIP trunk kernel (csrc/tower.hip).
+    """ResidualTower leaf evaluation on the fused HIP trunk kernel (csrc/tower.hip: host side; kernels in csrc/tower_kernels.h).
 
     The stem, every BasicBlock and the two 1x1 head convs run in one launch with
     the activations resident in LDS; the three small linear heads (policy
@@ -335,7 +335,7 @@ class HipTowerEvaluator(Evaluator):
         self.lo_w = t.linear_output.weight.detach().to(dev, bf)
         self.lo_b = t.linear_output.bias.detach().to(dev, bf)
         self.ff, self.cells = ff, cells
-        # fused-heads blobs (csrc/tower_heads.h k_heads)
+        # fused-heads blobs (csrc/tower_heads.h k_heads_co)
         K = cells * ff
         wp = torch.zeros(32, K, dtype=bf, device=dev)
         wp[: self.A] = self.lp_w
@@ -406,7 +406,7 @@ class HipTowerEvaluator(Evaluator):
             raise self._lib.tower_error("spmcts_tower_forward_dev", rc)
 
     def heads_dev(self, count_dev, max_rows):
-        """The linear-heads half of forward_dev (k_heads) on the current stream."""
+        """The linear-heads half of forward_dev (k_heads_co) on the current stream."""
         feats, probs, values = self._dev_bufs
         c = self._lib.ctypes.c_void_p
         stream = c(torch.cuda.current_stream().cuda_stream)

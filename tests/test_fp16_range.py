@@ -1,6 +1,6 @@
 """CPU: the fp16 fused tower cannot overflow on the bench's nets.
 
-The fp16 trunk (csrc/tower.hip, SPMCTS_TOWER_F16) keeps every layer's output in fp16 between layers,
+The fp16 trunk (csrc/tower_kernels.h and the family headers it includes, SPMCTS_TOWER_F16) keeps every layer's output in fp16 between layers,
 as the reference's own inference does under fp16 autocast (inference_worker.py:117).  fp16's largest
 finite value is 65504.  Here the bench's networks as bench.py builds them (ResidualTower(7, 6, 7,
 num_blocks=20, filter_factor=32 / 64), torch.manual_seed(0), BatchNorm at init statistics; configs 2
