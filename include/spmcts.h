@@ -72,7 +72,8 @@ enum spmcts_player_kind {
 #define SPMCTS_ERR_TAPE 0x2u      /* RNG tape exhausted                            */
 #define SPMCTS_ERR_NOCHILD 0x4u   /* select reached a node whose children are all invalid */
 #define SPMCTS_ERR_ACTION 0x8u    /* play_action on an illegal action              */
-#define SPMCTS_ERR_STATE 0x10u    /* inconsistent tree state                       */
+#define SPMCTS_ERR_STATE 0x10u    /* inconsistent tree state (also: a move chosen, or a root advanced, while
+                                     the tree's search still has sims to start or replies to make) */
 #define SPMCTS_ERR_EXPORT 0x20u   /* move export ring overflow                     */
 
 typedef struct spmcts_config {
@@ -213,6 +214,15 @@ int spmcts_set_leaf_peer(spmcts_arena *h, spmcts_arena *leader);
  * leader-served step without it fails (-4). */
 int spmcts_peer_push(spmcts_arena *h, float *probs_dev, float *values_dev, const float *leader_probs_dev,
                      const float *leader_values_dev, spmcts_stream stream, spmcts_stream leader_stream);
+/* Sim cap (search_threads > 1): the simulations one tree may start in one kernel launch.  A tree that reaches
+ * it pauses at a simulation boundary and the next launch resumes its slot cycle at exactly that point, so a
+ * tree whose sims end on terminal leaves (which wait for no network) no longer holds up the launch for every
+ * other tree; the operations, their order and the RNG draws are unchanged, so results are bit-identical for
+ * every cap.  0 = off; 0 < cap < 2 * search_threads is refused (-3): from 2 * search_threads on a search
+ * takes no more launches than without a cap.  Default: on, 2 * search_threads. */
+int spmcts_set_sim_cap(spmcts_arena *h, int32_t cap);
+/* (sync) tree-launches that paused at the sim cap since the arena was created */
+int spmcts_get_sim_pauses(spmcts_arena *h, int64_t *pauses_out);
 /* Evaluation cache (round 6; search_threads > 1 with leaf dedup on): the network
  * outputs of the arena's own leaf rows are kept, keyed like leaf dedup ((own, opp) stones from the mover's
  * view), for `window` generations -- one generation per spmcts_games_begin_ply / spmcts_search_begin, so

@@ -127,6 +127,8 @@ _SIGS = {
     "spmcts_set_leaf_dedup": [_P, _I32],
     "spmcts_set_leaf_peer": [_P, _P],
     "spmcts_peer_push": [_P, _P, _P, _P, _P, _P, _P],
+    "spmcts_set_sim_cap": [_P, _I32],
+    "spmcts_get_sim_pauses": [_P, ctypes.POINTER(_I64)],
     "spmcts_set_eval_cache": [_P, _I32, _I32],
     "spmcts_eval_cache_clear": [_P],
     "spmcts_leaf_trees": [_P, _P, _P],

@@ -236,6 +236,17 @@ class Arena:
         call("spmcts_set_eval_cache", self.h, int(window), int(capacity_log2))
         self.eval_cache = int(window)
 
+    def set_sim_cap(self, cap):
+        """Sims one tree may start per kernel launch (include/spmcts.h spmcts_set_sim_cap): 0 = off, else at
+        least 2 * search_threads.  Results do not depend on it."""
+        call("spmcts_set_sim_cap", self.h, int(cap))
+
+    def sim_pauses(self):
+        """Tree-launches that paused at the sim cap so far (sync)."""
+        n = ctypes.c_int64()
+        call("spmcts_get_sim_pauses", self.h, ctypes.byref(n))
+        return n.value
+
     def eval_cache_clear(self):
         call("spmcts_eval_cache_clear", self.h)
 

@@ -1,4 +1,4 @@
-// arena_expand.h — tree search, second half: k_expand, the threaded expand, _play, k_search_end, set_node, k_play_action.
+// arena_expand.h — tree search, second half: k_expand, the threaded expand and select (one slot-cycle walk), _play, k_search_end, set_node, k_play_action.
 // Included by spmcts.hip after arena_rows.h: needs the select helpers and the cache record layout.
 // ----------------------------------------------------------------------------
 // kernel: expand + backup of network-evaluated leaves (mcts.py:316-321, :94-98)
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(64) void k_expand(View v, const float *probs0, cons
     nd_n<P>(v, nb + leaf) = v.leaf_n[tree] + 1;
     nd_w<P>(v, nb + leaf) = v.leaf_w[tree] + val;
     v.used[tree] = blk + 1;
-    v.need[tree] = 0;
+    v.need[tree] = NEED_EMPTY;
     v.cnt[(size_t)tree * C_NCNT + C_NN] += 1;
     v.cnt[(size_t)tree * C_NCNT + C_HWM] = max(v.cnt[(size_t)tree * C_NCNT + C_HWM], (int64_t)(blk + 1));
   }
@@ -60,6 +60,10 @@ __global__ __launch_bounds__(64) void k_expand(View v, const float *probs0, cons
 // search has sims left, refill the slot at once (the rolling schedule above).  Read-modify-write:
 // earlier slots of the same tree have changed the shared ancestors.  Pending leaves of trees that
 // are not searching (a _set_node expansion, slot 0, path length 0) are completed without a refill.
+// The slots are walked cyclically from the tree's resume point (View::tres; arena_select.h "sim cap"): a
+// slot's reply takes its outputs from its row (NEED_ROW: evaluated by the network launch before this one) or
+// from the stash (NEED_STASH), and a launch that pauses at the cap leaves the outputs of the slots it has not
+// replied yet in the stash.
 // ----------------------------------------------------------------------------
 // (The body is a function of its own, inlined into the kernel: hipcc optimises it before it inlines it, and
 // written straight into the kernel the prefetch below lost its merged LDS stores.)
@@ -68,12 +72,21 @@ __global__ __launch_bounds__(64) void k_expand(View v, const float *probs0, cons
 // the other lane's trunk: 256 threads measured +0.6 % on the bench against 64 and +0.4 % against 128, every
 // run above every run of either ("Packed launch domain").
 constexpr int EXPAND_THREADS = 256;
+// k_select_vl, the first step of a search (and every step of a host loop that selects per step), is the same
+// walk without rows (ROWS false): no network launch precedes it, so a NEED_ROW slot is not evaluated yet and
+// ends the walk; empty slots are filled and NEED_STASH slots replied.  The latter matters to host loops that
+// skip the expand of a step without rows: a paused tree's stashed replies then still run, in the select.  One
+// wave per workgroup there: workgroups of 2..8 waves were measured slower for the once-per-ply first fill, as
+// were LDS copies of the child blocks a tree's sims read (the isolated expand 250 -> 295-300 us: a launch
+// starts with no copies, so most blocks are copied once and read once, and the levels of a sim are a chain of
+// short dependent LDS / permute / FP64 latencies, not memory round trips): DESIGN.md §4.
+constexpr int SELECT_THREADS = 64;
 
-template <class G>
+template <class G, int THREADS, bool ROWS>
 __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, const float *values0,
                                                const float *probs1, const float *values1) {
   constexpr int P = G::APAD;
-  constexpr int GPB = EXPAND_THREADS / P;
+  constexpr int GPB = THREADS / P;
   constexpr int KMAX = P;  // slots whose records one lane each prefetches (spmcts_arena_create: K <= P)
   __shared__ int32_t s_node[GPB][G::MAXD], s_n[GPB][G::MAXD], s_vl[GPB][G::MAXD], s_cs[GPB][G::MAXD];
   __shared__ double s_w[GPB][G::MAXD];
@@ -99,6 +112,7 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
   // the j-th path node of each slot; the tree's counters
   const int psl = tree * K + (lane < K ? lane : 0);
   const int my_need = lane < K ? (int)v.need[psl] : 0;
+  const int res = v.tres[tree];
   const int my_srow = v.srow[psl], my_leaf = v.leaf[psl], my_plen = v.plen[psl];
   const int my_mover = v.lmover[psl];
   const uint64_t my_pos = v.lpos[psl], my_neg = v.lneg[psl];
@@ -110,10 +124,12 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
 #pragma unroll
     for (int j = 0; j < KMAX; ++j) s_pnode[grp][j][lane] = pn[j];
   }
-  if (!group_or<P>(my_need)) return;
+  // nothing pending and no paused fill: the tree takes no part in this step
+  if (ROWS && !group_or<P>(my_need) && !(res & RES_FILL)) return;
   const int limit = min(v.budget[tree], v.iters);
   int started = v.tstarted[tree];
   const bool refill = started < limit;
+  if (!ROWS && !refill) return;  // a select: searching trees only
   int used = v.used[tree];
   const bool noise = v.noise_on[tree] != 0;
   const double nz = (noise && lane < G::A) ? v.noise[(size_t)tree * P + lane] : 0.0;
@@ -131,11 +147,15 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
       const int nj = __shfl(my_need, gbase + j, 64), row = __shfl(my_srow, gbase + j, 64);
       pr[j] = 0.f;
       vr[j] = 0.f;
-      if (j < K && nj) {
+      if (ROWS && j < K && nj == NEED_ROW) {
         const bool s1 = row >= v.seg1;
         const float *prow = s1 ? probs1 + (size_t)(row - v.seg1) * G::A : probs0 + (size_t)row * G::A;
         if (lane < G::A) pr[j] = prow[lane];
         vr[j] = s1 ? values1[row - v.seg1] : values0[row];
+      } else if (j < K && nj == NEED_STASH) {  // evaluated in an earlier step, kept across a pause
+        const size_t sj = (size_t)tree * K + j;
+        pr[j] = v.stash_p[sj * P + lane];
+        vr[j] = v.stash_v[sj];
       }
     }
 #pragma unroll
@@ -146,12 +166,24 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
   }
   bool terr = false;
   SimCnt sc;
+  // the cycle from the resume slot, once round (a slot met again was filled in this launch: its reply is the
+  // next launch's); a searching tree cycles over its own kt slots, any other over all K (its one pending slot)
+  const int kt = refill ? v.tK[tree] : K;
+  int j = res >> 1, nst = 0;
+  if ((unsigned)j >= (unsigned)kt) j = 0;  // (a tree whose sims in flight were lowered since its last search)
+  if ((res & RES_FILL) && (!refill || __shfl(my_need, gbase + j, 64))) {
+    if (lane == 0) set_err(v, SPMCTS_ERR_STATE);  // a paused fill is of an empty slot of a searching tree
+    return;
+  }
+  int paused_at = -1;  // iterations done when the cap paused the tree
   // one copy of the slot body (a rolled loop: the unrolled form was 70 KB of code, more than the
   // instruction cache two CUs share, for a kernel that runs one wave per CU on a latency chain)
 #pragma unroll 1
-  for (int j = 0; j < K; ++j) {
+  for (int i = 0; i < kt; ++i, j = j + 1 == kt ? 0 : j + 1) {
     const int ps = tree * K + j;
-    if (__shfl(my_need, gbase + j, 64)) {
+    const int nj = __shfl(my_need, gbase + j, 64);
+    if (!ROWS && nj == NEED_ROW) break;  // not evaluated: the cycle goes on at this reply, in an expand
+    if (nj != NEED_EMPTY) {
       const int leaf = __shfl(my_leaf, gbase + j, 64), plen = __shfl(my_plen, gbase + j, 64);
       const int mover = __shfl(my_mover, gbase + j, 64);
       const uint64_t lpos = __shfl(my_pos, gbase + j, 64), lneg = __shfl(my_neg, gbase + j, 64);
@@ -239,7 +271,7 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
       }
       if (lane == 0) {
         v.used[tree] = blk + 1;
-        v.need[ps] = 0;
+        v.need[ps] = NEED_EMPTY;
       }
       sc.nn += 1;
       sc.hwm = max(sc.hwm, (int64_t)(blk + 1));
@@ -261,8 +293,30 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
           R.cw += val;
         }
       }
-      if (refill && fill_slot_vl<G>(v, tree, j, limit, started, R, rng, terr, pl, noise, nz, sc, sf) == SIM_ERROR)
-        break;  // sticky SPMCTS_ERR_STATE; counters flushed below
+    }
+    if (refill) {
+      const int r = fill_slot_vl<G>(v, tree, j, limit, started, nst, R, rng, terr, pl, noise, nz, sc, sf);
+      if (r == SIM_ERROR) break;  // sticky SPMCTS_ERR_STATE; counters flushed below
+      if (r == SIM_PAUSED) {
+        paused_at = i;
+        break;
+      }
+    }
+  }
+  if (paused_at >= 0) {
+    // the cycle goes on at slot j's fill; the slots after it whose rows this launch read keep their outputs
+    // (lane a < A: prob a, lane 0: the value; their need was NEED_ROW, the stash of a NEED_STASH slot stands)
+    sc.pause += 1;
+    int q = j;
+    for (int i = paused_at + 1; i < kt; ++i) {
+      q = q + 1 == kt ? 0 : q + 1;
+      if (!ROWS || __shfl(my_need, gbase + q, 64) != NEED_ROW) continue;
+      const size_t sq = (size_t)tree * K + q;
+      v.stash_p[sq * P + lane] = s_pr[grp][q][lane];
+      if (lane == 0) {
+        v.stash_v[sq] = s_vr[grp][q];
+        v.need[sq] = NEED_STASH;
+      }
     }
   }
   if (lane == 0) {
@@ -270,6 +324,8 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
   }
   if (refill && lane == 0) {
     v.tstarted[tree] = started;
+    // a complete cycle ends where it began (j is back there), at that slot's reply
+    v.tres[tree] = j * 2 + (paused_at >= 0 ? RES_FILL : 0);
     if (terr) set_err(v, SPMCTS_ERR_TAPE);
     rng_store(v, tree, rng);
   }
@@ -278,7 +334,13 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
 template <class G>
 __global__ __launch_bounds__(EXPAND_THREADS) void k_expand_vl(View v, const float *probs0, const float *values0,
                                                   const float *probs1, const float *values1) {
-  expand_vl_body<G>(v, probs0, values0, probs1, values1);
+  expand_vl_body<G, EXPAND_THREADS, true>(v, probs0, values0, probs1, values1);
+}
+
+// (its domain: the active list, View::dn = its length, dpack = 1: spmcts_select_tree)
+template <class G>
+__global__ __launch_bounds__(SELECT_THREADS) void k_select_vl(View v) {
+  expand_vl_body<G, SELECT_THREADS, false>(v, nullptr, nullptr, nullptr, nullptr);
 }
 
 // ----------------------------------------------------------------------------
@@ -310,6 +372,9 @@ __device__ PlayOut play_move_choice(const View &v, int tree, double temp, float 
   const int root = v.root[tree];
   const int cb = nd_c<P>(v, nb + root);
   PlayOut o{0, false, 0.0, 0};
+  // the move is chosen from a complete search: every search_node call started, every reply made (the sim cap
+  // moves work between launches and must never leave any behind: arena_select.h "sim cap")
+  if (v.K > 1 && (!tree_idle(v, tree) || v.tstarted[tree] < min(v.budget[tree], v.iters))) set_err(v, SPMCTS_ERR_STATE);
   int n[G::A];
   for (int j = 0; j < G::A; ++j) n[j] = cb >= 0 ? nd_n<P>(v, nb + (size_t)cb * P + j) : 0;
   double t = temp;
@@ -419,6 +484,7 @@ __device__ bool set_node(const View &v, int tree, int a) {
       if (v.tstrong[tree]) nd_f<P>(v, nb + child) = 1;
     } else {
       const int ps = tree * v.K;  // pending slot 0 of the tree
+      if (!tree_idle(v, tree)) set_err(v, SPMCTS_ERR_STATE);  // the slot is taken only from an idle tree
       v.plen[ps] = 0;
       v.leaf[ps] = child;
       v.leaf_n[ps] = 0;
@@ -426,7 +492,7 @@ __device__ bool set_node(const View &v, int tree, int a) {
       v.lpos[ps] = b.pos;
       v.lneg[ps] = b.neg;
       v.lmover[ps] = (int8_t)rp;
-      v.need[ps] = 1;
+      v.need[ps] = NEED_ROW;
     }
   }
   v.root[tree] = child;

@@ -85,7 +85,9 @@ __global__ void k_rng_init(View v, uint64_t seed, uint64_t sub0) {
   v.rng[t] = s;
   v.tape_cur[t] = 0;
   ((int64_t *)v.tape_end)[t] = 0;
-  for (int j = 0; j < v.K; ++j) v.need[(size_t)t * v.K + j] = 0;
+  // (trees that are never reset are still walked by the full-width launches: every per-tree word they read)
+  for (int j = 0; j < v.K; ++j) v.need[(size_t)t * v.K + j] = NEED_EMPTY;
+  v.tres[t] = 0;
   v.tstarted[t] = 0x3fffffff;
   v.noise_on[t] = 0;
   v.tnet[t] = 0;

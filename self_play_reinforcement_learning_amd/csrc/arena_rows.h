@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void k_dedup_insert(View v) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= v.dn * v.K) return;
   const int t = dom_slot(v, c);
-  if (t < 0 || !v.need[t]) return;
+  if (t < 0 || v.need[t] != NEED_ROW) return;  // (a NEED_STASH slot is evaluated already: no row, here and below)
   uint64_t own, opp;
   leaf_key<G>(v, t, own, opp);
   const unsigned long long mine = ((unsigned long long)v.dgen << 32) | (uint32_t)t;
@@ -147,9 +147,9 @@ __global__ __launch_bounds__(256) void k_dedup_owner(View v) {
   const int t = dom_slot(v, c);
   int d = 0;
   if (t >= 0 && !v.dedup) {
-    d = v.need[t] != 0;  // no dedup: every pending leaf owns its row
+    d = v.need[t] == NEED_ROW;  // no dedup: every leaf that waits for the network owns its row
   } else if (t >= 0) {
-    const bool own = v.need[t] && (int)(uint32_t)v.dtab[v.dent[t]] == t;
+    const bool own = v.need[t] == NEED_ROW && (int)(uint32_t)v.dtab[v.dent[t]] == t;
     d = own ? (v.cwin && cache_hit<G>(v, t) ? 3 : 1) : 0;
     v.down[t] = (uint8_t)d;
     if (own && v.lead) {
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void k_dedup_owner_peer(View v, const uint64_t
     return;
   }
   int d = 0, xp = -1;
-  if (v.need[t] && (int)(uint32_t)v.dtab[v.dent[t]] == t) {
+  if (v.need[t] == NEED_ROW && (int)(uint32_t)v.dtab[v.dent[t]] == t) {
     d = 1;
     if (v.cwin && cache_hit<G>(v, t)) {  // the follower's own cache first: no wait on the leader's outputs
       v.down[t] = 3;
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void k_cache_io(View v, float *probs0, float *
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= v.dn * v.K) return;
   const int t = dom_slot(v, c);
-  if (t < 0 || !v.need[t]) return;
+  if (t < 0 || v.need[t] != NEED_ROW) return;
   const int d = v.down[t];
   if (d == 0) return;
   const int A = v.A;
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256) void k_dedup_alias(View v) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= v.dn * v.K) return;
   const int t = dom_slot(v, c);
-  if (t < 0 || !v.need[t]) return;
+  if (t < 0 || v.need[t] != NEED_ROW) return;
   const int s = (int)(uint32_t)v.dtab[v.dent[t]];
   if (s != t) v.srow[t] = v.srow[s];
 }

@@ -1,4 +1,4 @@
-// arena_select.h — tree search, first half: resets and noise, k_compact, the DPP reductions, k_select, the threaded select.
+// arena_select.h — tree search, first half: resets and noise, k_compact, the DPP reductions, k_select, the threaded sim (sim_vl) and slot fill, the sim cap.
 // Included by spmcts.hip after arena_rng.h: needs View, the node accessors and TreeRng.
 // ----------------------------------------------------------------------------
 // small helpers
@@ -34,7 +34,16 @@ __device__ __forceinline__ void reset_tree(const View &v, int tree, int player, 
   v.rplayer[tree] = (int8_t)player;
   v.noise_on[tree] = 0;
   v.tstarted[tree] = 0x3fffffff;  // no search in progress
-  for (int j = 0; j < v.K; ++j) v.need[(size_t)tree * v.K + j] = 0;
+  v.tres[tree] = 0;
+  for (int j = 0; j < v.K; ++j) v.need[(size_t)tree * v.K + j] = NEED_EMPTY;
+}
+
+// No pending slot, evaluated or not, and no paused fill: the state a search begins in, a move is chosen in
+// (with every search_node call started) and _set_node's expansion takes slot 0 in.
+__device__ __forceinline__ bool tree_idle(const View &v, int tree) {
+  int busy = v.tres[tree] & RES_FILL;
+  for (int j = 0; j < v.K; ++j) busy |= v.need[(size_t)tree * v.K + j] != NEED_EMPTY;
+  return !busy;
 }
 
 // terminal value of _expand_node (mcts.py:305-313) for `tree`'s own strong_play; r = reward * mover
@@ -81,6 +90,8 @@ __device__ void draw_noise(const View &v, int tree) {
   for (int j = 0; j < G::A; ++j) v.noise[(size_t)tree * G::APAD + j] = g[j];
   v.noise_on[tree] = 1;
   v.tstarted[tree] = 0;  // a search begins: `iterations` search_node calls to start
+  if (!tree_idle(v, tree)) set_err(v, SPMCTS_ERR_STATE);
+  v.tres[tree] = 0;  // its slot cycle starts at slot 0 (empty: nothing to reply, so with its fill)
 }
 
 // ----------------------------------------------------------------------------
@@ -451,7 +462,7 @@ __global__ __launch_bounds__(64) void k_select(View v, int n_active) {
           v.lpos[tree] = nb2.pos;
           v.lneg[tree] = nb2.neg;
           v.lmover[tree] = (int8_t)player;
-          v.need[tree] = 1;
+          v.need[tree] = NEED_ROW;
         }
         if (terr) set_err(v, SPMCTS_ERR_TAPE);
         rng_store(v, tree, rng);
@@ -489,7 +500,32 @@ __global__ __launch_bounds__(64) void k_select(View v, int n_active) {
 // oracle/mcts.py (OracleTree.search, threads=K) restates exactly this schedule; the G6 fixture
 // (threaded_stats.json) pins its statistics to the reference's own threaded search.
 // ----------------------------------------------------------------------------
-enum { SIM_DONE = 0, SIM_PENDING = 1, SIM_LEAK = 2, SIM_ERROR = -1 };
+enum { SIM_DONE = 0, SIM_PENDING = 1, SIM_LEAK = 2, SIM_PAUSED = 3, SIM_ERROR = -1 };
+
+// ----------------------------------------------------------------------------
+// sim cap.  A tree's search is one fixed sequence of operations -- reply slot 0, fill slot 0, reply slot 1,
+// fill slot 1, ... cyclically over its kt slots (OracleTree.search) -- and the only outside constraint is that
+// a slot's reply comes after the network evaluated its leaf.  Which launch runs which operation is free.  A
+// fill keeps starting sims until one waits for the network, and terminal leaves and leaks do not wait: a tree
+// on a forced win or loss runs dozens of sims in one launch while every other tree's group is done, and the
+// launch lasts as long as its slowest tree.  So a tree that has started View::simcap sims in a launch pauses
+// before the next one (never inside a sim) and the next launch goes on at exactly that point: the same
+// operations in the same order with the same RNG draws, so results are bit-identical for every cap.  At a
+// pause the launch's usual end-of-launch stores describe the tree completely (tstarted, the RNG state, the
+// paths' virtual losses, used, TreeRoot's write-through); on top of them View::tres holds the slot the cycle
+// goes on at, and the slots whose evaluated outputs the launch had not yet replied keep them in the stash
+// (NEED_STASH), since their rows are rewritten by the next step.
+//
+// Invariant (why a search needs no more launches than without a cap): cap >= 2 K.  A launch walks the cycle
+// from the resume point until it meets a slot filled in this same launch (not yet evaluated), i.e. it either
+// completes a full cycle of kt fills or pauses having started cap >= 2 K >= 2 kt sims.  Every fill starts at
+// least one sim while sims are left, so by induction started >= min(limit, kt * (launch + 1)) after each
+// launch, as in the uncapped schedule: a paused tree is ahead of that schedule, never behind it, and the
+// launch after a pause completes a full cycle again (every slot pending at its start was evaluated before it).
+// spmcts_set_sim_cap refuses 0 < cap < 2 K; k_games_end_ply and k_search_end raise SPMCTS_ERR_STATE if a
+// tree's search is not complete when its move is chosen.
+// ----------------------------------------------------------------------------
+constexpr int SIM_CAP_PER_K = 2;  // default cap = SIM_CAP_PER_K * K (spmcts_arena_create)
 
 // The searching tree's root, loaded once per kernel and kept in registers across the K fills /
 // backups / refills (it is on every path): node id, its child block (fixed during a search: the
@@ -574,8 +610,9 @@ struct StoreFence {
 // The tree's counters of one kernel launch (the same value in every lane of the group), added to the
 // arena's counters once at the end of the launch instead of a read-modify-write per sim.
 struct SimCnt {
-  int64_t sims = 0, depth = 0, term = 0, leak = 0, nn = 0, hwm = 0;
+  int64_t sims = 0, depth = 0, term = 0, leak = 0, nn = 0, hwm = 0, pause = 0;
   __device__ void flush(int64_t *cnt) const {
+    if (pause) cnt[C_PAUSE] += pause;
     cnt[C_SIMS] += sims;
     cnt[C_DEPTH] += depth;
     cnt[C_TERM] += term;
@@ -752,7 +789,7 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
           v.lpos[ps] = nb2.pos;
           v.lneg[ps] = nb2.neg;
           v.lmover[ps] = (int8_t)player;
-          v.need[ps] = 1;
+          v.need[ps] = NEED_ROW;
         }
       }
       if (!done && lcs == kUncached) sf.dirty = true;
@@ -776,62 +813,21 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
   }
 }
 
-// Refill pending slot j: start sims until one waits for the network or the tree's budget of
-// search_node calls is spent (`started` counts them, mcts.py:328-331 submits `iterations`).  No fence
+// Refill pending slot j: start sims until one waits for the network, the tree's budget of
+// search_node calls is spent (`started` counts them, mcts.py:328-331 submits `iterations`), or the launch has
+// started View::simcap sims of this tree (`nst` counts them; SIM_PAUSED, before a sim and never in one).  No fence
 // between sims: a sim reads the root and its children from the registers, and StoreFence's `dirty` rule fences
 // before any global read of node records after a store to one.
 template <class G>
-__device__ int fill_slot_vl(const View &v, int tree, int j, int limit, int &started, TreeRoot &R, TreeRng &rng,
-                            bool &terr, const PathLds &pl, bool noise, double nz, SimCnt &sc, StoreFence &sf) {
+__device__ int fill_slot_vl(const View &v, int tree, int j, int limit, int &started, int &nst, TreeRoot &R,
+                            TreeRng &rng, bool &terr, const PathLds &pl, bool noise, double nz, SimCnt &sc,
+                            StoreFence &sf) {
   while (started < limit) {
+    if (v.simcap && nst >= v.simcap) return SIM_PAUSED;
     ++started;
+    ++nst;
     const int r = sim_vl<G>(v, tree, j, R, rng, terr, pl, noise, nz, sc, sf);
     if (r == SIM_PENDING || r == SIM_ERROR) return r;
   }
   return SIM_DONE;
-}
-
-// First step of a search: fill the K slots of every searching tree.  One wave of 64 threads: 64/P trees, a
-// P-lane group each.  (LDS copies of the child blocks a tree's sims read, 16 per tree, were measured slower --
-// the isolated expand 250 -> 295-300 us, select unchanged: a launch starts with no copies, so most blocks are
-// copied once and read once, and the levels of a sim are a chain of short dependent LDS / permute / FP64
-// latencies, not memory round trips -- and removed, as were workgroups of 2..8 waves for this kernel, once per
-// ply: DESIGN.md §4.  k_expand_vl, once per step, runs four waves per workgroup: EXPAND_THREADS.)
-template <class G>
-__global__ __launch_bounds__(64) void k_select_vl(View v, int n_active) {
-  constexpr int P = G::APAD;
-  constexpr int GPB = 64 / P;
-  __shared__ int32_t s_node[GPB][G::MAXD], s_n[GPB][G::MAXD], s_vl[GPB][G::MAXD], s_cs[GPB][G::MAXD];
-  __shared__ double s_w[GPB][G::MAXD];
-  const int lane = threadIdx.x & (P - 1);
-  const int grp = threadIdx.x / P;
-  const PathLds pl{s_node[grp], s_n[grp], s_vl[grp], s_cs[grp], s_w[grp]};
-  StoreFence sf;
-  const int slot = blockIdx.x * (int)(blockDim.x / P) + grp;  // blockDim = 64: GPB trees
-  if (slot >= n_active) return;
-  const int tree = v.active[slot];
-  if (tree < 0) return;
-  const int limit = min(v.budget[tree], v.iters);
-  int started = v.tstarted[tree];
-  if (started >= limit) return;
-  const bool noise = v.noise_on[tree] != 0;
-  const double nz = (noise && lane < G::A) ? v.noise[(size_t)tree * P + lane] : 0.0;
-  TreeRng rng;
-  rng_load(v, tree, rng);
-  TreeRoot R = load_root<G>(v, tree);
-  bool terr = false;
-  SimCnt sc;
-  const int kt = v.tK[tree];  // this tree's sims in flight (its own thread_count, <= K)
-  for (int j = 0; j < kt; ++j) {
-    if (v.need[tree * v.K + j]) continue;
-    // SIM_ERROR (a corrupt tree: the sticky SPMCTS_ERR_STATE flag is set) ends the tree's launch; the counters
-    // of the sims completed before it are still flushed below (the failing sim's path vl is not written)
-    if (fill_slot_vl<G>(v, tree, j, limit, started, R, rng, terr, pl, noise, nz, sc, sf) == SIM_ERROR) break;
-  }
-  if (lane == 0) {
-    sc.flush(v.cnt + (size_t)tree * C_NCNT);
-    v.tstarted[tree] = started;
-    if (terr) set_err(v, SPMCTS_ERR_TAPE);
-    rng_store(v, tree, rng);
-  }
 }

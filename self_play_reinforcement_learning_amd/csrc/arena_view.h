@@ -37,7 +37,13 @@ struct View {
   double *leaf_w;
   uint64_t *lpos, *lneg;
   int8_t *lmover;
-  uint8_t *need;
+  uint8_t *need;      // per pending slot: NEED_EMPTY, NEED_ROW or NEED_STASH (below)
+  // the sim cap (K > 1, arena_select.h "sim cap"): where the tree's slot cycle goes on in the next launch
+  // (tres [T]: slot * 2 + RES_FILL), and the network outputs of NEED_STASH slots (stash_p [NS][P] probs,
+  // stash_v [NS] value); simcap = sims a tree may start per launch (0 = no cap)
+  int32_t *tres;
+  float *stash_p, *stash_v;
+  int simcap;
   Philox *rng;
   const double *tape;
   const int64_t *tape_end;  // [T] end offset
@@ -157,8 +163,15 @@ __host__ __device__ __forceinline__ uint32_t &nd_vm(const View &v, size_t gb) {
   return *(uint32_t *)(v.nodes + gb * (size_t)NodeRec<P>::BYTES + NodeRec<P>::VM);
 }
 
-enum { C_SIMS = 0, C_NN = 1, C_TERM = 2, C_DEPTH = 3, C_SETNODE = 4, C_MOVES = 5, C_LEAK = 6, C_GC = 7, C_HWM = 8, C_NCNT = 10 };
+enum { C_SIMS = 0, C_NN = 1, C_TERM = 2, C_DEPTH = 3, C_SETNODE = 4, C_MOVES = 5, C_LEAK = 6, C_GC = 7, C_HWM = 8, C_PAUSE = 9, C_NCNT = 10 };
 enum { GS_IDLE = 0, GS_ACTIVE = 1, GS_DONE = 2 };
+// View::need of a pending slot.  NEED_ROW: its leaf waits for a network row (the only state the row pipeline
+// sees: dedup, scan, alias, encode, cache, peer push).  NEED_STASH: the network has evaluated the leaf, its
+// outputs are in View::stash_p / stash_v, and the reply has not run yet (a launch that paused at the sim cap).
+enum { NEED_EMPTY = 0, NEED_ROW = 1, NEED_STASH = 2 };
+// View::tres bit 0: the resume slot's reply is done and its fill was cut short by the cap (the tree is paused
+// with sims left to start, whether or not a slot is pending); clear: the cycle goes on with the slot's reply
+enum { RES_FILL = 1 };
 
 __device__ __forceinline__ void set_err(const View &v, uint32_t f) { atomicOr(v.err, f); }
 

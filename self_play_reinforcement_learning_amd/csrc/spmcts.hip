@@ -28,9 +28,9 @@
 // included below in this order:
 //   arena_view.h    device view (View), NodeRec accessors, set_err, nbase
 //   arena_rng.h     Philox / tape RNG
-//   arena_select.h  resets and noise, k_compact, DPP reductions, k_select, threaded select
+//   arena_select.h  resets and noise, k_compact, DPP reductions, k_select, the threaded sim and slot fill
 //   arena_rows.h    leaf dedup, evaluation cache, peer push, k_scan_need, k_encode
-//   arena_expand.h  k_expand, threaded expand, _play, k_search_end, set_node, k_play_action
+//   arena_expand.h  k_expand, threaded expand and select (one slot-cycle walk), _play, k_search_end, set_node, k_play_action
 //   arena_games.h   game state machine, export
 //   arena_misc.h    k_env_step, k_table_net, k_copy_probe, the init kernels
 //
@@ -215,6 +215,9 @@ static void plan_arena(spmcts_arena *h, Plan &pl) {
   pl.add(&v.lneg, NS);
   pl.add(&v.lmover, NS);
   pl.add(&v.need, NS);
+  pl.add(&v.tres, T);
+  pl.add(&v.stash_p, v.K > 1 ? NS * P : 1);  // the sim cap's stash: APAD probs and one value per pending slot
+  pl.add(&v.stash_v, v.K > 1 ? NS : 1);
   pl.add(&v.rng, T);
   pl.add((int64_t **)&v.tape_end, T);
   pl.add(&v.tape_cur, T);
@@ -297,6 +300,7 @@ static int setup_view(spmcts_arena *h, const spmcts_config *cfg) {
   if (v.K > P) return fail(-3, "search_threads must not exceed the lane group (8 for connect4, 16 for tictactoe)");
   v.iters = std::max(1, cfg->iterations);
   v.NS = v.T * v.K;
+  v.simcap = v.K > 1 ? SIM_CAP_PER_K * v.K : 0;  // on by default (spmcts_set_sim_cap)
   v.dn = v.T;  // full width (set_domain)
   v.dpack = 0;
   v.seg1 = v.NS;
@@ -518,7 +522,10 @@ static bool peer_live(const spmcts_arena *h) { return h->peer && h->v.dedup && h
 // restricts to the list anyway).  set_node (k_games_end_ply, k_play_action) sets it for slot 0 of trees that do
 // not search, and the launch_rows that follows it is never a simulation step: it and its expand run at full
 // width and clear those slots before the next ply's list is written.  A listed tree's own slots are all
-// cleared by the last step's expand (every pending slot of a domain tree is completed there), so nothing
+// cleared by the last step's expand: without the sim cap every pending slot of a domain tree is completed in
+// each step's expand; with it a paused tree carries pending and stashed slots (NEED_STASH: evaluated, no row --
+// every kernel here takes only NEED_ROW slots) from step to step, but never past the search's last step
+// (arena_select.h "sim cap": cap >= 2 K; k_games_end_ply raises SPMCTS_ERR_STATE otherwise), so nothing
 // carries over when the other tree of the game searches next.  The list ascends (active[g] = 2 g + mover), so
 // compact order is slot order and k_scan_need numbers the same rows as at full width.  A caller's list
 // (spmcts_search_begin) may be in any order: those searches, and every end-of-ply launch, stay at full width.
@@ -582,7 +589,9 @@ int spmcts_select_tree(spmcts_arena *h, spmcts_stream stream) {
   int rc = 0;
   if (n > 0) {  // one P-lane group per tree, 64 / P groups per block
     const long long lanes = (long long)n * h->P;
-    rc = h->v.K > 1 ? LAUNCH(h, k_select_vl, lanes, 64, s, h->v, n) : LAUNCH(h, k_select, lanes, 64, s, h->v, n);
+    View dv = h->v;  // k_select_vl walks the active list as a packed domain
+    set_domain(h, dv, true);
+    rc = h->v.K > 1 ? LAUNCH(h, k_select_vl, lanes, SELECT_THREADS, s, dv) : LAUNCH(h, k_select, lanes, 64, s, h->v, n);
   }
   h->v.sim += h->v.K;
   return rc;
@@ -695,6 +704,25 @@ int spmcts_set_root_prior_net(spmcts_arena *h, int32_t net, const float *probs_d
 int spmcts_set_leaf_dedup(spmcts_arena *h, int32_t on) {
   if (!h) return fail(-1, "null arena");
   h->v.dedup = (on && h->v.K > 1) ? 1 : 0;  // K = 1 keeps one row per tree (k_expand walks rows)
+  return 0;
+}
+
+int spmcts_set_sim_cap(spmcts_arena *h, int32_t cap) {
+  if (!h) return fail(-1, "null arena");
+  // below 2 K a search could need more launches than ceil(iterations / K) + 1 (arena_select.h "sim cap")
+  if (cap < 0 || (cap > 0 && cap < 2 * h->v.K)) return fail(-3, "sim cap: 0 (off) or at least 2 * search_threads");
+  h->v.simcap = h->v.K > 1 ? cap : 0;
+  return 0;
+}
+
+int spmcts_get_sim_pauses(spmcts_arena *h, int64_t *pauses_out) {
+  if (!h || !pauses_out) return fail(-1, "null argument");
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<int64_t> c((size_t)h->v.T * C_NCNT);
+  HIP_TRY(hipMemcpy(c.data(), h->v.cnt, c.size() * 8, hipMemcpyDeviceToHost));
+  int64_t n = 0;
+  for (int t = 0; t < h->v.T; ++t) n += c[(size_t)t * C_NCNT + C_PAUSE];
+  *pauses_out = n;
   return 0;
 }
 
