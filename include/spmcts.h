@@ -78,7 +78,7 @@ enum spmcts_player_kind {
 
 typedef struct spmcts_config {
   int32_t game;            /* enum spmcts_game                                               */
-  int32_t width, height;   /* 7x6 Connect4, 3x3 TicTacToe (only these are instantiated)      */
+  int32_t width, height;   /* Connect4 7x6, 6x5, 8x7; TicTacToe 3x3 (only these are instantiated) */
   int32_t n_trees;         /* tree slots (games mode needs >= 2*n_games)                     */
   int32_t n_games;         /* game slots for the self-play state machine (0 = tree mode only) */
   int32_t iterations;      /* simulations per move (mcts.py:125, sizes the node pool)        */
@@ -311,7 +311,7 @@ int spmcts_table_net(int32_t game, int32_t width, int32_t height, const void *le
  * inference_worker.py:117) MFMA with fp32 accumulation.  planes_dev: bf16 [batch][W][H][3]
  * (NHWC leaf rows, 0/1 planes); weights and features_dev [batch][W*H][channels/2] (policy |
  * value head channels, cell-major) in the flags' element type.  Packed weight/bias layout:
- * csrc/tower_kernels.h (the M16 layout's block convs: csrc/tower_m16.h).  Instantiated for 7x6 and 3x3 boards with channels 128 or 256. */
+ * csrc/tower_kernels.h (the M16 layout's block convs: csrc/tower_m16.h).  Instantiated for 7x6 and 3x3 boards with channels 128 or 256 (libspmcts_boards.so: the same six entry points for 6x5 and 8x7). */
 #define SPMCTS_TOWER_F16 2
 int spmcts_tower_forward(int32_t width, int32_t height, int32_t channels, int32_t n_blocks, const void *planes_dev,
                          int32_t batch, const void *weights_dev, const float *bias_dev, void *features_dev,

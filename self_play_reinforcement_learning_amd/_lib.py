@@ -184,6 +184,42 @@ def lib():
     return _lib
 
 
+# The add-on library (csrc/tower_boards.hip): the fused trunk and heads of the Connect4 variant boards 6x5 and
+# 8x7.  It exports the six tower entry points below with the product library's signatures and is loaded the
+# first time a shape the product library does not hold is asked for.  SPMCTS_BOARDS_LIB names another file.
+BOARDS_LIB_PATH = os.environ.get("SPMCTS_BOARDS_LIB", os.path.join(_HERE, "libspmcts_boards.so"))
+TOWER_SYMBOLS = ("spmcts_tower_supported", "spmcts_tower_weight_layout", "spmcts_tower_forward",
+                 "spmcts_tower_forward_dev", "spmcts_tower_heads", "spmcts_tower_heads_dev")
+_boards = None
+
+
+def boards_lib():
+    """The add-on library's handle, or None where it has not been built (the variant boards then run on the
+    PyTorch evaluator)."""
+    global _boards
+    if _boards is None:
+        if not os.path.exists(BOARDS_LIB_PATH):
+            return None
+        L = ctypes.CDLL(BOARDS_LIB_PATH)
+        for name in TOWER_SYMBOLS:
+            f = getattr(L, name)
+            f.argtypes = _SIGS[name]
+            f.restype = ctypes.c_int
+        _boards = L
+    return _boards
+
+
+def tower_lib(width, height, channels):
+    """The library whose fused trunk holds this shape: the product library, else the add-on library, else None."""
+    L = lib()
+    if L.spmcts_tower_supported(width, height, channels):
+        return L
+    B = boards_lib()
+    if B is not None and B.spmcts_tower_supported(width, height, channels):
+        return B
+    return None
+
+
 # environment switches read only by the A/B library (libspmcts_ab.so); the product library refuses them with
 # SPMCTS_ERR_AB_SWITCH (-5, include/spmcts.h) rather than silently ignoring them
 AB_SWITCHES = ("SPMCTS_TOWER_C256", "SPMCTS_HEADS", "SPMCTS_HEADS_C256")

@@ -5,6 +5,10 @@ library launches on `torch.cuda.current_stream()` of that device, so the
 network that consumes the leaf rows runs on the same stream with no extra
 synchronisation.  The only host round trip per simulation is reading the
 number of leaf rows (`select()` returns it as a Python int).
+
+Instantiated boards (`GAMES`): "connect4" (7x6), "connect4_6_5" (6x5), "connect4_8_7" (8x7) and "tictactoe"
+(3x3), all in libspmcts.so.  The fused trunk of the 7x6 and 3x3 nets is in libspmcts.so too; that of the 6x5
+and 8x7 nets is in the add-on library libspmcts_boards.so (`_lib.tower_lib`).
 """
 import ctypes
 
@@ -14,7 +18,10 @@ import torch
 from . import _lib
 from ._lib import call, ptr
 
-GAMES = {"connect4": (_lib.CONNECT4, 7, 6, 7), "tictactoe": (_lib.TICTACTOE, 3, 3, 9)}
+# name -> (game id, width, height, actions): the boards csrc/spmcts.hip with_game instantiates.  The Connect4
+# variants carry the reference's variant_string() names (Connect4Env(6, 5) / Connect4Env(8, 7)).
+GAMES = {"connect4": (_lib.CONNECT4, 7, 6, 7), "tictactoe": (_lib.TICTACTOE, 3, 3, 9),
+         "connect4_6_5": (_lib.CONNECT4, 6, 5, 6), "connect4_8_7": (_lib.CONNECT4, 8, 7, 8)}
 LEAF_FORMATS = {"f32": _lib.LEAF_F32, "f16": _lib.LEAF_F16, "bf16": _lib.LEAF_BF16, "board": _lib.LEAF_BOARD_I64}
 _LEAF_DTYPES = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16, "board": torch.int64}
 
@@ -24,21 +31,25 @@ def game_of_env(env):
 
     Accepts this package's envs and the reference's Connect4Env / TicTacToeEnv
     (games/connect4/connect4env.py, games/tictactoe/tictactoe_env.py) by shape.
+    A Connect4 env of an instantiated size maps to its variant_string() name: "connect4" (7x6),
+    "connect4_6_5", "connect4_8_7"; any other size raises a ValueError that lists the instantiated boards.
     """
     e = env() if isinstance(env, type) else env
     name = type(e).__name__.lower()
     w, h = getattr(e, "width", None), getattr(e, "height", None)
     n = e.action_space.n if hasattr(e, "action_space") else getattr(e, "n_actions", None)
     if "connect4" in name or (w, h, n) == (7, 6, 7):
-        game = "connect4"
+        gid = _lib.CONNECT4
     elif "tictactoe" in name or (w, h, n) == (3, 3, 9):
-        game = "tictactoe"
+        gid = _lib.TICTACTOE
     else:
         raise ValueError(f"unsupported environment {type(e).__name__}")
-    gid, W, H, A = GAMES[game]
-    if (w, h) != (W, H):
-        raise ValueError(f"{game} arena is instantiated for {W}x{H} boards only, got {w}x{h}")
-    return game
+    for game, (g, W, H, A) in GAMES.items():
+        if g == gid and (w, h) == (W, H):
+            return game
+    kind = "connect4" if gid == _lib.CONNECT4 else "tictactoe"
+    built = ", ".join(f"{W}x{H} ({game})" for game, (g, W, H, A) in GAMES.items() if g == gid)
+    raise ValueError(f"the {kind} arena is instantiated for these boards only: {built}; got {w}x{h}")
 
 
 def _stream():

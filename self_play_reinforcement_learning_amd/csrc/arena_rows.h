@@ -86,7 +86,9 @@ constexpr int CACHE_PROBES = 32;
 constexpr unsigned long long CACHE_READY = 1ull, CACHE_BUSY = 2ull;
 
 constexpr int CACHE_REC = 8;  // u64 words per record (64 bytes): tag, own, opp, (A + 1) f32 (A <= 9)
-static_assert(24 + 4 * (C4::A + 1) <= 8 * CACHE_REC && 24 + 4 * (TTT::A + 1) <= 8 * CACHE_REC, "cache record");
+static_assert(24 + 4 * (C4::A + 1) <= 8 * CACHE_REC && 24 + 4 * (TTT::A + 1) <= 8 * CACHE_REC &&
+                  24 + 4 * (C4_6x5::A + 1) <= 8 * CACHE_REC && 24 + 4 * (C4_8x7::A + 1) <= 8 * CACHE_REC,
+              "cache record");
 
 __device__ __forceinline__ unsigned long long *cache_rec(const View &v, uint32_t h) {
   return (unsigned long long *)v.crec + (size_t)h * CACHE_REC;

@@ -33,6 +33,11 @@ struct Geo {
 
 using C4 = Geo<7, 6, 4, true>;
 using TTT = Geo<3, 3, 3, false>;
+// The reference's Connect4Env(width, height) variants "connect4_6_5" and "connect4_8_7".  8x7 sits on the
+// limits: W * (H + 1) = 64 fills the mask (highest cell bit 62; bit 63 is the last column's sentinel, always
+// zero, and is what leaf_key uses to tell the two networks apart), and A == APAD == 8 leaves no idle lane.
+using C4_6x5 = Geo<6, 5, 4, true>;
+using C4_8x7 = Geo<8, 7, 4, true>;
 
 struct Board {
   uint64_t pos;  // pieces of +1

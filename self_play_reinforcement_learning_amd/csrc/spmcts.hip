@@ -143,21 +143,25 @@ static bool cache_view(const spmcts_arena *h, View &v) {
   return true;
 }
 
-// The one (game, width, height) switch: f(G{}) for the instantiated game type G, else -2 with `unsupported`.
+// The one (game, width, height) switch, and the one list of instantiated boards: f(G{}) for the game type G,
+// else -2 with UNSUPPORTED.  Every per-game kernel launch goes through it (LAUNCH below).
+static const char *const UNSUPPORTED =
+    "unsupported game/board size (instantiated: connect4 7x6, connect4 6x5, connect4 8x7, tictactoe 3x3)";
 template <class F>
-static int with_game(int game, int width, int height, const char *unsupported, F &&f) {
+static int with_game(int game, int width, int height, F &&f) {
   if (game == SPMCTS_CONNECT4 && width == 7 && height == 6) return f(C4{});
+  if (game == SPMCTS_CONNECT4 && width == 6 && height == 5) return f(C4_6x5{});
+  if (game == SPMCTS_CONNECT4 && width == 8 && height == 7) return f(C4_8x7{});
   if (game == SPMCTS_TICTACTOE && width == 3 && height == 3) return f(TTT{});
-  return fail(-2, unsupported);
+  return fail(-2, UNSUPPORTED);
 }
 
 static int geometry(const spmcts_config *c, int *A, int *P, int *cells, int *maxd, int *maxm) {
-  return with_game(c->game, c->width, c->height,
-                   "unsupported game/board size (instantiated: connect4 7x6, tictactoe 3x3)", [&](auto g) {
-                     using G = decltype(g);
-                     *A = G::A; *P = G::APAD; *cells = G::CELLS; *maxd = G::MAXD; *maxm = G::MAXM;
-                     return 0;
-                   });
+  return with_game(c->game, c->width, c->height, [&](auto g) {
+    using G = decltype(g);
+    *A = G::A; *P = G::APAD; *cells = G::CELLS; *maxd = G::MAXD; *maxm = G::MAXM;
+    return 0;
+  });
 }
 
 // worst-case node blocks per tree per game: root pseudo block + root children + one
@@ -297,7 +301,7 @@ static int setup_view(spmcts_arena *h, const spmcts_config *cfg) {
   v.leaf_format = cfg->leaf_format;
   v.leaf_layout = cfg->leaf_layout;
   v.K = std::max(1, cfg->search_threads);
-  if (v.K > P) return fail(-3, "search_threads must not exceed the lane group (8 for connect4, 16 for tictactoe)");
+  if (v.K > P) return fail(-3, "search_threads must not exceed the lane group (8 for the connect4 boards, 16 for tictactoe)");
   v.iters = std::max(1, cfg->iterations);
   v.NS = v.T * v.K;
   v.simcap = v.K > 1 ? SIM_CAP_PER_K * v.K : 0;  // on by default (spmcts_set_sim_cap)
@@ -329,9 +333,9 @@ static int launch(void (*k)(P...), long long n, int B, hipStream_t s, const A &.
   if (e != hipSuccess) return fail(-(int)e - 1000, std::string("launch: ") + hipGetErrorString(e));
   return 0;
 }
-// launch() of a kernel template on the game: k<C4> or k<TTT>, by the arena's game
+// launch() of a kernel template on the arena's game type: k<G>, G from with_game
 #define LAUNCH(h, k, n, B, s, ...) \
-  ((h)->cfg.game == SPMCTS_CONNECT4 ? launch(k<C4>, n, B, s, __VA_ARGS__) : launch(k<TTT>, n, B, s, __VA_ARGS__))
+  with_game((h)->cfg.game, (h)->W, (h)->H, [&](auto game_) { return launch(k<decltype(game_)>, n, B, s, __VA_ARGS__); })
 
 extern "C" {
 
@@ -965,7 +969,7 @@ int spmcts_env_step(int32_t game, int32_t width, int32_t height, const int8_t *b
                     int8_t *reward_dev, uint8_t *done_dev, int8_t *status_dev, uint8_t *valid_dev,
                     spmcts_stream stream) {
   if (n <= 0) return 0;
-  return with_game(game, width, height, "unsupported game/board size", [&](auto g) {
+  return with_game(game, width, height, [&](auto g) {
     return launch(k_env_step<decltype(g)>, n, 256, (hipStream_t)stream, boards_dev, actions_dev, players_dev, over_dev,
                   n, out_boards_dev, reward_dev, done_dev, status_dev, valid_dev);
   });
@@ -973,7 +977,7 @@ int spmcts_env_step(int32_t game, int32_t width, int32_t height, const int8_t *b
 
 int spmcts_env_step_host(int32_t game, int32_t width, int32_t height, int8_t *board, int32_t action, int32_t player,
                          int32_t *reward, int32_t *done) {
-  return with_game(game, width, height, "unsupported game/board size", [&](auto g) {
+  return with_game(game, width, height, [&](auto g) {
     using G = decltype(g);
     if (action < 0 || action >= G::A) return fail(-3, "action out of range");
     Board b = from_cells<G>(board);
@@ -988,7 +992,7 @@ int spmcts_env_step_host(int32_t game, int32_t width, int32_t height, int8_t *bo
 }
 
 int spmcts_valid_moves_host(int32_t game, int32_t width, int32_t height, const int8_t *board, uint8_t *valid) {
-  return with_game(game, width, height, "unsupported game/board size", [&](auto g) {
+  return with_game(game, width, height, [&](auto g) {
     using G = decltype(g);
     const uint32_t m = legal_mask<G>(from_cells<G>(board));
     for (int a = 0; a < G::A; ++a) valid[a] = (m >> a) & 1u;
@@ -1000,7 +1004,7 @@ int spmcts_table_net(int32_t game, int32_t width, int32_t height, const void *le
                      int32_t leaf_layout, int32_t n, uint64_t salt, const uint64_t *salts_dev, float *probs_dev,
                      float *values_dev, spmcts_stream stream) {
   if (n <= 0) return 0;
-  return with_game(game, width, height, "unsupported game/board size", [&](auto g) {
+  return with_game(game, width, height, [&](auto g) {
     return launch(k_table_net<decltype(g)>, n, 128, (hipStream_t)stream, leaves_dev, leaf_format, leaf_layout, n, salt,
                   salts_dev, probs_dev, values_dev);
   });

@@ -94,7 +94,8 @@ class _BitboardEnv(BaseEnv):
 
 
 class Connect4Env(_BitboardEnv):
-    """connect4env.py:11-101 (7x6 is the instantiated size)."""
+    """connect4env.py:11-101.  The arena is instantiated for 7x6 ("connect4") and the variants 6x5
+    ("connect4_6_5") and 8x7 ("connect4_8_7"): variant_string() is the arena's game name (arena.GAMES)."""
 
     GAME = _lib.CONNECT4
     DEFAULT_WIDTH = 7

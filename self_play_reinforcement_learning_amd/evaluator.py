@@ -170,8 +170,8 @@ def make_evaluator(network, game, device=None, dtype=torch.bfloat16, leaf_layout
             return HipTowerEvaluator(network, device=device, dtype=dtype)
         if backend == "auto":
             logging.getLogger(__name__).info(
-                "fused HIP tower not instantiated for %s x %s boards with %d channels (built: 7x6 / 3x3, C = 128 or "
-                "256): leaf evaluation runs on the PyTorch TowerEvaluator (MIOpen convolutions, %s)",
+                "fused HIP tower not instantiated for %s x %s boards with %d channels (built: 7x6 / 3x3, and 6x5 / 8x7 "
+                "in the add-on library libspmcts_boards.so, C = 128 or 256): leaf evaluation runs on the PyTorch TowerEvaluator (MIOpen convolutions, %s)",
                 W, H, 4 * int(getattr(network, "filter_factor", 0)), dtype)
         return TowerEvaluator(network, dtype=dtype, leaf_layout=leaf_layout, device=device)
     if isinstance(network, nn.Module):
@@ -271,7 +271,10 @@ class HipTowerEvaluator(Evaluator):
         self.device = device
         self.C = 4 * tower.filter_factor
         self.W, self.H, self.A = tower.width, tower.height, tower.action_size
-        if not _lib.lib().spmcts_tower_supported(self.W, self.H, self.C):
+        # the library that holds this shape's trunk and heads: the product library (7x6, 3x3) or the add-on
+        # library of the variant boards (6x5, 8x7: _lib.boards_lib)
+        self._tl = _lib.tower_lib(self.W, self.H, self.C)
+        if self._tl is None:
             raise ValueError(f"fused tower not instantiated for {self.W}x{self.H} boards, {self.C} channels")
         self.refresh()
 
@@ -291,7 +294,7 @@ class HipTowerEvaluator(Evaluator):
         from . import _lib
 
         C = 4 * getattr(tower, "filter_factor", 0)
-        return bool(_lib.lib().spmcts_tower_supported(tower.width, tower.height, C))
+        return _lib.tower_lib(tower.width, tower.height, C) is not None
 
     @torch.no_grad()
     def refresh(self):
@@ -304,7 +307,7 @@ class HipTowerEvaluator(Evaluator):
         w, b = fold(t.conv1, t.bn1)
         dt = self.dtype
         # the blob layout the library's trunk for this shape expects (include/spmcts.h SPMCTS_WLAYOUT_*)
-        self.wlayout = self._lib.lib().spmcts_tower_weight_layout(self.W, self.H, self.C)
+        self.wlayout = self._tl.spmcts_tower_weight_layout(self.W, self.H, self.C)
         m16 = self.wlayout == self._lib.WLAYOUT_M16
         ws.append(_pack_conv(w, cin_pad=16, dtype=dt))
         bs.append(b)
@@ -392,7 +395,7 @@ class HipTowerEvaluator(Evaluator):
         feats, probs, values = self._dev_bufs
         c = self._lib.ctypes.c_void_p
         stream = c(torch.cuda.current_stream().cuda_stream)
-        L = self._lib.lib()
+        L = self._tl
         timer = getattr(self, "tower_timer", None)
         if timer is not None:
             timer.start()
@@ -410,7 +413,7 @@ class HipTowerEvaluator(Evaluator):
         feats, probs, values = self._dev_bufs
         c = self._lib.ctypes.c_void_p
         stream = c(torch.cuda.current_stream().cuda_stream)
-        rc = self._lib.lib().spmcts_tower_heads_dev(self.W, self.H, self.C, self.A, c(feats.data_ptr()),
+        rc = self._tl.spmcts_tower_heads_dev(self.W, self.H, self.C, self.A, c(feats.data_ptr()),
                                                     c(count_dev.data_ptr()), max_rows, c(self.head_w.data_ptr()),
                                                     c(self.head_b.data_ptr()), c(probs.data_ptr()),
                                                     c(values.data_ptr()), self.flags, stream)
@@ -425,7 +428,7 @@ class HipTowerEvaluator(Evaluator):
         feats = torch.empty((max(n, 1), self.cells, self.C // 2), dtype=self.dtype, device=planes_nhwc.device)
         if n:
             stream = torch.cuda.current_stream().cuda_stream
-            rc = self._lib.lib().spmcts_tower_forward(
+            rc = self._tl.spmcts_tower_forward(
                 self.W, self.H, self.C, self.n_blocks, self._lib.ctypes.c_void_p(planes_nhwc.data_ptr()), n,
                 self._lib.ctypes.c_void_p(self.wblob.data_ptr()), self._lib.ctypes.c_void_p(self.bblob.data_ptr()),
                 self._lib.ctypes.c_void_p(feats.data_ptr()), self.flags, self._lib.ctypes.c_void_p(stream))
@@ -458,7 +461,7 @@ class HipTowerEvaluator(Evaluator):
             value = torch.empty(max(n, 1), dtype=torch.float32, device=f.device)
             if n:
                 c = self._lib.ctypes.c_void_p
-                rc = self._lib.lib().spmcts_tower_heads(
+                rc = self._tl.spmcts_tower_heads(
                     self.W, self.H, self.C, self.A, c(f.data_ptr()), n, c(self.head_w.data_ptr()),
                     c(self.head_b.data_ptr()), c(probs.data_ptr()), c(value.data_ptr()), self.flags,
                     c(torch.cuda.current_stream().cuda_stream))
