@@ -282,6 +282,44 @@ int spmcts_export_moves(spmcts_arena *h, int8_t *states_dev, float *tree_probs_d
 /* (sync) per-slot game state: active flag, ply, swap, game id */
 int spmcts_games_state(spmcts_arena *h, uint8_t *active, int32_t *ply, uint8_t *swap, int64_t *game_id);
 
+/* (sync) per-slot game outcome, host arrays of n_games entries (each may be NULL): result = the reward in the
+ * view of tree 2g (+1 win, 0 draw or unfinished, -1 loss: r * player, selfplayworker.py:218), swap, plies
+ * played, state (0 idle, 1 active, 2 done and not yet finished by spmcts_games_finish_ply).  A slot keeps its
+ * values after its game is finished until another game starts in it, so an arena that plays one game per slot
+ * (no refill) reads every game's outcome here (the per-pairing results of compare_models, elo.py:49-71). */
+int spmcts_games_results(spmcts_arena *h, int8_t *result, uint8_t *swap, int32_t *ply, uint8_t *state);
+
+/* ---- league: N networks in one arena (Elo.compare_models(*names), games/algos/elo.py:73-100) ---------------- */
+/* A league arena is a single-network arena (spmcts_set_tree_players nets all 0) whose trees send their leaves
+ * to one of n_nets networks: the step's rows are numbered and encoded as always, spmcts_league_route copies
+ * each network's rows into that network's segment of a second buffer, each network evaluates its segment, and
+ * spmcts_league_unroute brings the outputs back into arena-row order for the unchanged spmcts_expand.  Every
+ * leaf is evaluated on its own (InferenceWorker, inference_worker.py:89-119): no dedup, no evaluation cache.
+ *
+ * (sync) tree_net: host array of n_trees entries in [0, n_nets), or -1 for a tree that sends no leaves (a
+ * hard-coded player); 1 <= n_nets <= 32.  Network j's routed segment starts at seg[j] = K * (trees of networks
+ * < j) and holds K * (trees of network j) rows (K = search_threads; a tree never has more than K pending rows,
+ * and the end-of-ply expansions are at most one per tree).  -3 when leaf dedup, the evaluation cache or a leaf
+ * peer is on or the arena is a two-network arena; turning one of those on afterwards fails the same way.
+ * tree_net NULL with n_nets 0 turns the league off. */
+int spmcts_set_league(spmcts_arena *h, const int32_t *tree_net, int32_t n_nets);
+/* seg[0 .. n_nets]: first routed row of each network; seg[n_nets] = the routed buffer's rows in use. */
+int spmcts_league_segments(const spmcts_arena *h, int32_t *seg);
+/* The rows of the last select / leaf_rows / play_action / games_end_ply (leaves_dev, row_bytes bytes each;
+ * leaf_count_dev = that call's count buffer, read on the device; NULL = the arena's own copy): network j's
+ * rows to routed rows [seg[j], seg[j] + net_count_dev[j]) in ascending arena-row order.  A stable partition by
+ * per-workgroup histograms and a scan (no atomics): the same layout every run.  row_bytes: any even number;
+ * both buffers 2-byte aligned at least.  The row -> routed-row map stays in the arena for the unroute.  A row
+ * of a tree without a network raises SPMCTS_ERR_STATE.  No host synchronisation. */
+int spmcts_league_route(spmcts_arena *h, const void *leaves_dev, const int32_t *leaf_count_dev, int32_t row_bytes,
+                        void *routed_dev, int32_t *net_count_dev /*[n_nets]*/, spmcts_stream stream);
+/* probs_by_net_dev / values_by_net_dev: device arrays of n_nets device pointers to each network's outputs
+ * ([rows][A] f32 / [rows] f32, indexed from that network's routed row 0).  Writes probs_dev [rows][A] and
+ * values_dev [rows] in arena-row order.  -4 unless spmcts_league_route ran on this step's rows. */
+int spmcts_league_unroute(spmcts_arena *h, const float *const *probs_by_net_dev,
+                          const float *const *values_by_net_dev, float *probs_dev, float *values_dev,
+                          spmcts_stream stream);
+
 /* ---- diagnostics --------------------------------------------------------- */
 int spmcts_get_counters(spmcts_arena *h, spmcts_counters *out); /* (sync) */
 int spmcts_check(spmcts_arena *h);                                /* (sync) <0 if a device error flag is set */

@@ -9,7 +9,8 @@ Public API mirrors the reference:
     ResidualTower                         (games/general/modules.py)
     Connect4Env, TicTacToeEnv             (games/connect4, games/tictactoe)
     OneStepLookahead, Random              (games/general/hardcoded_players.py)
-plus the arena itself: Arena, SelfPlayEngine, LanedEngine, DeviceTableNet.
+    Elo, ModelDatabase                    (games/algos/elo.py, games/algos/model_database.py)
+plus the arena itself: Arena, SelfPlayEngine, LanedEngine, LeagueEngine, DeviceTableNet.
 """
 from .base_model import BasePlayer, ModelContainer, Policy, TrainableModel  # noqa: F401
 from .memory import Memory  # noqa: F401
@@ -19,6 +20,9 @@ _LAZY = {
     "Arena": ".arena",
     "SelfPlayEngine": ".engine",
     "LanedEngine": ".engine",
+    "LeagueEngine": ".engine",
+    "Elo": ".elo",
+    "ModelDatabase": ".elo",
     "DeviceTableNet": ".evaluator",
     "make_evaluator": ".evaluator",
     "MCTreeSearch": ".mcts",

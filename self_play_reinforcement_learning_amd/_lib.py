@@ -118,6 +118,11 @@ _SIGS = {
     "spmcts_games_finish_ply": [_P, _I32, _P, _P],
     "spmcts_export_moves": [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P],
     "spmcts_games_state": [_P, _P, _P, _P, _P],
+    "spmcts_games_results": [_P, _P, _P, _P, _P],
+    "spmcts_set_league": [_P, _P, _I32],
+    "spmcts_league_segments": [_P, _P],
+    "spmcts_league_route": [_P, _P, _P, _I32, _P, _P, _P],
+    "spmcts_league_unroute": [_P, _P, _P, _P, _P, _P],
     "spmcts_get_counters": [_P, ctypes.POINTER(Counters)],
     "spmcts_check": [_P],
     "spmcts_env_step": [_I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P],

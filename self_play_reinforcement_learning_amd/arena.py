@@ -467,6 +467,87 @@ class Arena:
         return dict(state=np.array(list(active)), ply=np.array(list(ply)), swap=np.array(list(swap)),
                     game_id=np.array(list(gid)))
 
+    def games_results(self):
+        """Per-slot outcome (include/spmcts.h spmcts_games_results; sync): result in tree 2g's view, swap, ply,
+        state.  A slot keeps them after its game finished until another game starts in it."""
+        G = self.n_games
+        res = np.zeros(G, dtype=np.int8)
+        swap = np.zeros(G, dtype=np.uint8)
+        ply = np.zeros(G, dtype=np.int32)
+        state = np.zeros(G, dtype=np.uint8)
+        torch.cuda.current_stream().synchronize()
+        call("spmcts_games_results", self.h, *[x.ctypes.data_as(ctypes.c_void_p) for x in (res, swap, ply, state)])
+        return dict(result=res, swap=swap, ply=ply, state=state)
+
+    # ------------------------------------------------------------------ league (N networks in one arena)
+    @property
+    def row_bytes(self):
+        """Bytes of one leaf row."""
+        return self._leaves[0].numel() * self._leaves.element_size()
+
+    def set_league(self, tree_net, n_nets=None):
+        """Per-tree network of a league arena (include/spmcts.h spmcts_set_league): `tree_net[t]` in
+        [0, n_nets), -1 for a tree that sends no leaves (a hard-coded player); None turns the league off.
+        Allocates the routed leaf buffer; `league_seg[j]` = network j's first routed row."""
+        torch.cuda.current_stream().synchronize()
+        if tree_net is None:
+            call("spmcts_set_league", self.h, None, 0)
+            self.n_nets, self.league_seg = 0, None
+            return
+        a = np.ascontiguousarray(np.asarray(tree_net, dtype=np.int32))
+        if a.shape != (self.n_trees,):
+            raise ValueError(f"expected {self.n_trees} per-tree entries, got {a.shape}")
+        n = int(a.max()) + 1 if n_nets is None else int(n_nets)
+        call("spmcts_set_league", self.h, a.ctypes.data_as(ctypes.c_void_p), n)
+        seg = (ctypes.c_int32 * (n + 1))()
+        call("spmcts_league_segments", self.h, seg)
+        self.n_nets, self.league_seg = n, list(seg)
+        if getattr(self, "_routed", None) is None:
+            self._routed = torch.zeros_like(self._leaves)
+        self._net_count = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        self._probs = torch.zeros((self.max_rows, self.A), dtype=torch.float32, device=self.device)
+        self._values = torch.zeros(self.max_rows, dtype=torch.float32, device=self.device)
+
+    def league_route(self, count_dev=None):
+        """The rows of the last select / leaf_rows / play_action / games_end_ply, partitioned by network into
+        the routed buffer (no host sync).  `count_dev`: the device row count (default: this arena's)."""
+        c = self._count if count_dev is None else count_dev
+        self._route_count = c  # alive until the unroute
+        call("spmcts_league_route", self.h, ptr(self._leaves), ptr(c), self.row_bytes, ptr(self._routed),
+             ptr(self._net_count), _stream())
+
+    def routed_from(self, net):
+        """Network `net`'s routed segment as the network's input tensor (every row it can hold)."""
+        lo, hi = self.league_seg[net], self.league_seg[net + 1]
+        x = self._routed[lo:hi]
+        if self.leaf_format != "board" and self.leaf_layout == "nhwc":
+            x = x.permute(0, 3, 1, 2)
+        return x
+
+    def net_count_dev(self, net):
+        """Device int32 holding network `net`'s routed row count of the last league_route."""
+        return self._net_count[net:net + 1]
+
+    def net_counts(self):
+        """Routed row count per network of the last league_route (sync)."""
+        return self._net_count.cpu().tolist()
+
+    def league_unroute(self, outputs):
+        """`outputs`: per network (probs f32 [rows, A], values f32 [rows]) indexed from the network's routed row
+        0.  Returns (probs, values) in arena-row order, ready for expand()."""
+        keep = [(p if p.dtype == torch.float32 and p.is_contiguous() else p.float().contiguous(),
+                 v.reshape(-1) if v.dtype == torch.float32 and v.is_contiguous() else v.float().reshape(-1).contiguous())
+                for p, v in outputs]
+        ptrs = tuple((p.data_ptr(), v.data_ptr()) for p, v in keep)
+        if getattr(self, "_out_ptrs", None) != ptrs:  # the pointer tables change only when a buffer moves
+            self._out_ptrs = ptrs
+            self._ptab = torch.tensor([a for a, _ in ptrs], dtype=torch.int64).to(self.device)
+            self._vtab = torch.tensor([b for _, b in ptrs], dtype=torch.int64).to(self.device)
+        self._out_keep = keep
+        call("spmcts_league_unroute", self.h, ptr(self._ptab), ptr(self._vtab), ptr(self._probs), ptr(self._values),
+             _stream())
+        return self._probs, self._values
+
     # ------------------------------------------------------------------ diagnostics
     def counters(self):
         c = _lib.Counters()

@@ -33,6 +33,7 @@
 //   arena_expand.h  k_expand, threaded expand and select (one slot-cycle walk), _play, k_search_end, set_node, k_play_action
 //   arena_games.h   game state machine, export
 //   arena_misc.h    k_env_step, k_table_net, k_copy_probe, the init kernels
+//   arena_league.h  league routing: a step's rows partitioned by their tree's network, and back
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see Makefile).
 #include <hip/hip_runtime.h>
@@ -88,6 +89,7 @@ static int fail(int code, const std::string &msg) {
 #include "arena_expand.h"
 #include "arena_games.h"
 #include "arena_misc.h"
+#include "arena_league.h"
 
 // ----------------------------------------------------------------------------
 // host side
@@ -119,7 +121,17 @@ struct spmcts_arena {
   // spmcts_expand2 use the same domain
   bool games_list = false;
   bool packed_step = false;
+  // league (spmcts_set_league): the trees' networks and the routing buffers (lg.n = 0: off), and whether a
+  // route of the current step's rows has run (spmcts_league_unroute needs it)
+  League lg = {};
+  std::vector<int32_t> lg_seg;
+  std::vector<void *> league_allocs;
+  bool route_step = false;
 };
+
+static bool league_on(const spmcts_arena *h) { return h->lg.n > 0; }
+static const char *const LEAGUE_EXCLUDES =
+    "a league arena is single-network and runs without leaf dedup, evaluation cache and leaf peer";
 
 // The launch domain of a step's per-slot kernels (View::dn, dpack): the active list, or every tree.
 static void set_domain(const spmcts_arena *h, View &v, bool packed) {
@@ -411,6 +423,7 @@ int spmcts_arena_destroy(spmcts_arena *h) {
   if (h->push_stream) (void)hipStreamDestroy(h->push_stream);
   for (void *p : h->allocs) (void)hipFree(p);
   for (void *p : h->cache_allocs) (void)hipFree(p);
+  for (void *p : h->league_allocs) (void)hipFree(p);
   delete h;
   return 0;
 }
@@ -426,6 +439,7 @@ int spmcts_set_leaf_peer(spmcts_arena *h, spmcts_arena *leader) {
   h->push_pending = false;
   if (!leader) return 0;
   if (leader == h) return fail(-3, "an arena cannot be its own leader");
+  if (league_on(h) || league_on(leader)) return fail(-3, LEAGUE_EXCLUDES);
   if (leader->peer || !h->followers.empty()) return fail(-3, "one level of lanes: a leader cannot follow");
   if (leader->cfg.game != h->cfg.game || leader->device != h->device)
     return fail(-3, "leader and follower must play the same game on the same device");
@@ -542,6 +556,7 @@ static bool peer_live(const spmcts_arena *h) { return h->peer && h->v.dedup && h
 // full-width passes rewrite down for every slot.
 static int launch_rows(spmcts_arena *h, void *leaves_dev, int32_t *leaf_count_dev, hipStream_t s, bool sim_step) {
   h->peer_step = false;
+  h->route_step = false;  // new rows: the last route's map is stale
   h->packed_step = sim_step && h->games_list;
   for (spmcts_arena *f : h->followers)  // a leader rewrites its table, keys and (later) outputs only after the pushes
     if (f->push_pending) {
@@ -659,6 +674,7 @@ int spmcts_set_tree_players(spmcts_arena *h, const uint8_t *nets, const uint8_t 
     if (budgets) bd[t] = budgets[t] < 0 ? 0x7fffffff : budgets[t];
     n0 += nt[t] ? 0 : 1;
   }
+  if (league_on(h) && n0 < T) return fail(-3, LEAGUE_EXCLUDES);
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(h->v.tnet, nt.data(), T, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->v.tkind, kd.data(), T, hipMemcpyHostToDevice));
@@ -707,6 +723,7 @@ int spmcts_set_root_prior_net(spmcts_arena *h, int32_t net, const float *probs_d
 
 int spmcts_set_leaf_dedup(spmcts_arena *h, int32_t on) {
   if (!h) return fail(-1, "null arena");
+  if (on && league_on(h)) return fail(-3, LEAGUE_EXCLUDES);
   h->v.dedup = (on && h->v.K > 1) ? 1 : 0;  // K = 1 keeps one row per tree (k_expand walks rows)
   return 0;
 }
@@ -734,6 +751,7 @@ int spmcts_set_eval_cache(spmcts_arena *h, int32_t window, int32_t capacity_log2
   if (!h) return fail(-1, "null arena");
   if (window < 0 || window > (1 << 20)) return fail(-3, "eval cache window out of range");
   if (capacity_log2 != 0 && (capacity_log2 < 10 || capacity_log2 > 28)) return fail(-3, "eval cache capacity_log2: 10..28 (0 = sized from the arena)");
+  if (window > 0 && league_on(h)) return fail(-3, LEAGUE_EXCLUDES);
   if (h->cache_step) return fail(-4, "a step that consulted the evaluation cache has not been expanded yet");
   for (const spmcts_arena *f : h->followers)
     if (f->cache_step && f->cache_shared_step)
@@ -916,6 +934,116 @@ int spmcts_games_state(spmcts_arena *h, uint8_t *active, int32_t *ply, uint8_t *
   if (ply) HIP_TRY(hipMemcpy(ply, h->v.gply, 4 * G, hipMemcpyDeviceToHost));
   if (swap) HIP_TRY(hipMemcpy(swap, h->v.gswap, G, hipMemcpyDeviceToHost));
   if (game_id) HIP_TRY(hipMemcpy(game_id, h->v.gid, 8 * G, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int spmcts_games_results(spmcts_arena *h, int8_t *result, uint8_t *swap, int32_t *ply, uint8_t *state) {
+  if (!h) return fail(-1, "null arena");
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t G = h->v.G;
+  if (!G) return 0;
+  if (result) HIP_TRY(hipMemcpy(result, h->v.gresult, G, hipMemcpyDeviceToHost));
+  if (swap) HIP_TRY(hipMemcpy(swap, h->v.gswap, G, hipMemcpyDeviceToHost));
+  if (ply) HIP_TRY(hipMemcpy(ply, h->v.gply, 4 * G, hipMemcpyDeviceToHost));
+  if (state) HIP_TRY(hipMemcpy(state, h->v.gstate, G, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- league ---------------------------------------------------------------
+int spmcts_set_league(spmcts_arena *h, const int32_t *tree_net, int32_t n_nets) {
+  if (!h) return fail(-1, "null arena");
+  if (!tree_net && n_nets == 0) {  // off
+    HIP_TRY(hipDeviceSynchronize());
+    h->lg.n = 0;
+    h->route_step = false;
+    return 0;
+  }
+  if (!tree_net) return fail(-1, "null argument");
+  if (n_nets < 1 || n_nets > LEAGUE_MAX_NETS) return fail(-3, "league: 1 .. 32 networks");
+  const View &v = h->v;
+  if (v.dedup || v.cwin || h->peer || !h->followers.empty() || v.seg1 < v.NS) return fail(-3, LEAGUE_EXCLUDES);
+  const int T = v.T;
+  std::vector<int32_t> seg(LEAGUE_MAX_NETS + 1, 0);
+  for (int t = 0; t < T; ++t) {
+    if (tree_net[t] < -1 || tree_net[t] >= n_nets) return fail(-3, "league: tree_net entries are -1 or in [0, n_nets)");
+    if (tree_net[t] >= 0) seg[tree_net[t] + 1] += v.K;  // K rows per tree of the network at most
+  }
+  for (int j = 0; j < LEAGUE_MAX_NETS; ++j) seg[j + 1] += seg[j];
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (h->league_allocs.empty()) {
+    const size_t blocks = ((size_t)v.NS + LEAGUE_SPAN - 1) / LEAGUE_SPAN;
+    const size_t bytes[5] = {4 * (size_t)T, 4 * (size_t)(LEAGUE_MAX_NETS + 1), 4 * (size_t)v.NS, 4 * (size_t)v.NS,
+                             4 * blocks * LEAGUE_MAX_NETS};
+    void *p[5] = {};
+    for (int i = 0; i < 5; ++i) {
+      const hipError_t e = hipMalloc(&p[i], bytes[i]);
+      if (e != hipSuccess) {
+        for (int j = 0; j < i; ++j) (void)hipFree(p[j]);
+        return fail(-1000 - (int)e, std::string("league hipMalloc: ") + hipGetErrorString(e));
+      }
+    }
+    h->league_allocs.assign(p, p + 5);
+    h->lg.tree_net = (int32_t *)p[0];
+    h->lg.seg = (int32_t *)p[1];
+    h->lg.rank = (int32_t *)p[2];
+    h->lg.map = (int32_t *)p[3];
+    h->lg.hist = (int32_t *)p[4];
+  }
+  HIP_TRY(hipMemcpy(h->lg.tree_net, tree_net, 4 * (size_t)T, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->lg.seg, seg.data(), 4 * seg.size(), hipMemcpyHostToDevice));
+  h->lg_seg = seg;
+  h->lg.n = n_nets;
+  h->route_step = false;
+  return 0;
+}
+
+int spmcts_league_segments(const spmcts_arena *h, int32_t *seg) {
+  if (!h || !seg) return fail(-1, "null argument");
+  if (!league_on(h)) return fail(-4, "not a league arena (spmcts_set_league)");
+  for (int j = 0; j <= h->lg.n; ++j) seg[j] = h->lg_seg[j];
+  return 0;
+}
+
+int spmcts_league_route(spmcts_arena *h, const void *leaves_dev, const int32_t *leaf_count_dev, int32_t row_bytes,
+                        void *routed_dev, int32_t *net_count_dev, spmcts_stream stream) {
+  if (!h || !leaves_dev || !routed_dev || !net_count_dev) return fail(-1, "null argument");
+  if (!league_on(h)) return fail(-4, "not a league arena (spmcts_set_league)");
+  if (row_bytes < 2 || (row_bytes & 1)) return fail(-3, "league: row_bytes must be a positive even number");
+  const uintptr_t a = (uintptr_t)leaves_dev | (uintptr_t)routed_dev | (uintptr_t)row_bytes;
+  if (a & 1) return fail(-3, "league: leaf rows must be 2-byte aligned");
+  const hipStream_t s = (hipStream_t)stream;
+  const View &v = h->v;
+  League lg = h->lg;
+  lg.count = leaf_count_dev ? leaf_count_dev : v.row_count;
+  h->lg.count = lg.count;
+  TRY(launch(k_league_hist, v.NS, LEAGUE_SPAN, s, v, lg));
+  TRY(launch(k_league_scan, 64, 64, s, v, lg, net_count_dev));
+  const int unit = (a & 15) == 0 ? 16 : (a & 7) == 0 ? 8 : (a & 3) == 0 ? 4 : 2;  // the widest aligned unit
+  const int upr = row_bytes / unit;
+  const long long n = std::min<long long>((long long)v.NS * upr, 256ll * LEAGUE_COPY_BLOCKS);
+  if (unit == 16)
+    TRY(launch(k_league_copy<uint4>, n, 256, s, v, lg, leaves_dev, routed_dev, upr));
+  else if (unit == 8)
+    TRY(launch(k_league_copy<uint2>, n, 256, s, v, lg, leaves_dev, routed_dev, upr));
+  else if (unit == 4)
+    TRY(launch(k_league_copy<uint32_t>, n, 256, s, v, lg, leaves_dev, routed_dev, upr));
+  else
+    TRY(launch(k_league_copy<uint16_t>, n, 256, s, v, lg, leaves_dev, routed_dev, upr));
+  h->route_step = true;
+  return 0;
+}
+
+int spmcts_league_unroute(spmcts_arena *h, const float *const *probs_by_net_dev, const float *const *values_by_net_dev,
+                          float *probs_dev, float *values_dev, spmcts_stream stream) {
+  if (!h || !probs_by_net_dev || !values_by_net_dev || !probs_dev || !values_dev) return fail(-1, "null argument");
+  if (!league_on(h)) return fail(-4, "not a league arena (spmcts_set_league)");
+  if (!h->route_step) return fail(-4, "spmcts_league_unroute needs spmcts_league_route of this step's rows first");
+  const View &v = h->v;
+  const long long n = std::min<long long>((long long)v.NS * (v.A + 1), 256ll * LEAGUE_COPY_BLOCKS);
+  TRY(launch(k_league_unroute, n, 256, (hipStream_t)stream, v, h->lg, probs_by_net_dev, values_by_net_dev, probs_dev,
+             values_dev));
+  h->route_step = false;
   return 0;
 }
 

@@ -1,0 +1,353 @@
+"""Rating models against each other: ModelDatabase + Elo (games/algos/model_database.py, games/algos/elo.py).
+
+    db = ModelDatabase("ratings/connect4", Connect4Env)
+    db.add_model("random", ModelContainer(Random))
+    db.add_model("net1", ModelContainer(MCTreeSearch, policy_kwargs=dict(network=net, iterations=200)))
+    elo = Elo(db)
+    elo.compare_models("random", "net1")      # every pairing in ONE league arena (engine.LeagueEngine)
+    elo.calculate_elo()                       # {"net1": ..., "random": 0}
+
+Departures from the reference, both deliberate:
+
+* The database is a directory of plain files instead of three shelves of pickles: `models.json` (name -> policy
+  class name, JSON-able policy kwargs, net shape), `weights/<name>.pt` (the network's state_dict, read with
+  weights_only=True), `results.json` and `elo.json`.  Nothing in it is executable.
+* `calculate_elo` fits the reference's model (elo.py:176-191: expected score q1 / (q1 + q2), q = 10^(r / 400),
+  binary cross-entropy against 1 / 0.5 / 0, the anchor fixed) but solves it as a deterministic full-batch
+  maximum-likelihood fit (damped Newton in float64, to a gradient norm below GRAD_TOL) where the reference runs
+  100,000 SGD steps on sampled batches of 32, and it adds `prior_draws` virtual draws (default 1) to every pair
+  that has played.  Without them a 100-0 score -- the common case against `random` -- has no finite maximum;
+  the reference's answer there is only where its step budget ran out.  `prior_draws=0` is the reference's
+  likelihood exactly.  The stale `self_play=` argument of elo.py:81 is not reproduced.
+
+Command line (the two rating commands of the reference's main.py):
+
+    python -m self_play_reinforcement_learning_amd.elo compare_models --dir D --g connect4 [--b W H] [--p names...]
+    python -m self_play_reinforcement_learning_amd.elo calculate_elo --dir D --g connect4 [--b W H]
+"""
+import itertools
+import json
+import math
+import os
+
+import numpy as np
+import torch
+
+from .base_model import ModelContainer
+
+POLICIES = ("MCTreeSearch", "Random", "OneStepLookahead")
+_JSON_SCALARS = (bool, int, float, str, type(None))
+
+
+def _jsonable(x):
+    if isinstance(x, _JSON_SCALARS):
+        return True
+    if isinstance(x, (list, tuple)):
+        return all(_jsonable(y) for y in x)
+    if isinstance(x, dict):
+        return all(isinstance(k, str) and _jsonable(y) for k, y in x.items())
+    return False
+
+
+def _read_json(path, default):
+    if not os.path.exists(path):
+        return default
+    with open(path) as f:
+        return json.load(f)
+
+
+def _write_json(path, obj):
+    tmp = path + ".tmp"
+    with open(tmp, "w") as f:
+        json.dump(obj, f, indent=1)  # (models.json keeps the registration order)
+    os.replace(tmp, path)
+
+
+class ModelDatabase:
+    """Registered models, the results of their games and their ratings, in one directory
+    (model_database.py:11-70; a directory of JSON files and state_dicts instead of shelves)."""
+
+    def __init__(self, directory, env):
+        self.directory = str(directory)
+        self.env = env() if isinstance(env, type) else env
+        os.makedirs(os.path.join(self.directory, "weights"), exist_ok=True)
+        self._models = os.path.join(self.directory, "models.json")
+        self._results = os.path.join(self.directory, "results.json")
+        self._elo = os.path.join(self.directory, "elo.json")
+
+    # ------------------------------------------------------------------ models
+    def models(self):
+        """name -> {"policy", "policy_kwargs", "net"} in registration order."""
+        return _read_json(self._models, {})
+
+    def add_model(self, name, container):
+        """Persist a ModelContainer under `name` (model_database.py:64-70).  ValueError on a name that is taken
+        or that contains "_" (the result keys are "a__b", elo.py:47-50)."""
+        if "_" in name:
+            raise ValueError(f"model name {name!r} contains '_' (result keys join two names with '__')")
+        models = self.models()
+        if name in models:
+            raise ValueError("Model name already in use")
+        gen = container.policy_gen
+        policy = gen if isinstance(gen, str) else gen.__name__
+        if policy == "OnestepLookahead":
+            policy = "OneStepLookahead"
+        if policy not in POLICIES:
+            raise ValueError(f"unknown policy {policy!r} (one of {', '.join(POLICIES)})")
+        kw = dict(container.policy_kwargs)
+        net = kw.get("network", kw.get("evaluator"))
+        entry = {"policy": policy, "net": None,
+                 "policy_kwargs": {k: v for k, v in kw.items()
+                                   if k not in ("network", "evaluator", "env", "env_gen", "memory_queue", "optim")
+                                   and _jsonable(v)}}
+        if policy == "MCTreeSearch":
+            if net is None:
+                raise ValueError("an MCTreeSearch model needs policy_kwargs['network']")
+            entry["net"] = {k: int(getattr(net, k)) for k in ("width", "height", "action_size", "num_blocks",
+                                                               "filter_factor")}
+            state = {k: v.detach().cpu() for k, v in net.state_dict().items()}
+            torch.save(state, os.path.join(self.directory, "weights", f"{name}.pt"))
+        models[name] = entry
+        _write_json(self._models, models)
+
+    def network(self, name):
+        """The registered network of an MCTreeSearch model (None for a hard-coded player)."""
+        entry = self.models()[name]
+        if entry["net"] is None:
+            return None
+        from .modules import ResidualTower
+
+        net = ResidualTower(**entry["net"])
+        state = torch.load(os.path.join(self.directory, "weights", f"{name}.pt"), weights_only=True,
+                           map_location="cpu")
+        net.load_state_dict(state)
+        return net.eval()
+
+    def get_model(self, name):
+        """The ModelContainer registered under `name` (KeyError if there is none)."""
+        import importlib
+
+        entry = self.models()[name]
+        mod = ".mcts" if entry["policy"] == "MCTreeSearch" else ".hardcoded_players"
+        gen = getattr(importlib.import_module(mod, __package__), entry["policy"])
+        kw = dict(entry["policy_kwargs"], env=self.env)
+        if entry["net"] is not None:
+            kw["network"] = self.network(name)
+        return ModelContainer(gen, policy_kwargs=kw)
+
+    # ------------------------------------------------------------------ results and ratings
+    def results(self):
+        """"a__b" (a > b) -> {"wins", "draws", "losses"} in a's view."""
+        return _read_json(self._results, {})
+
+    def set_results(self, results):
+        _write_json(self._results, results)
+
+    def elos(self):
+        """{"elo": {name: rating}} once calculate_elo has run (model_database.py:58-59), else {}."""
+        return _read_json(self._elo, {})
+
+    def set_elos(self, ratings):
+        _write_json(self._elo, {"elo": ratings})
+
+
+def result_key(model_1, model_2):
+    """The reference's key rule (elo.py:49-54): the lexicographically larger name first; swap = the results of
+    (model_1, model_2) have to be turned round to be in the first name's view."""
+    if model_1 == model_2:
+        raise ValueError("a model does not play itself")
+    if model_1 > model_2:
+        return f"{model_1}__{model_2}", False
+    return f"{model_2}__{model_1}", True
+
+
+def fit_elo(names, results, anchor_model, anchor_elo=0.0, prior_draws=1.0, grad_tol=None, max_iter=200):
+    """Maximum-likelihood ratings of `names` from `results` ("a__b" -> wins / draws / losses in a's view) under
+    the reference's model (see the module docstring); float64, damped Newton with step halving, until the
+    largest gradient component (per rating point) is below grad_tol (default Elo.GRAD_TOL).  Raises ValueError
+    if the played pairs do not connect every model to the anchor, RuntimeError if there is no finite maximum
+    (only with prior_draws = 0, where some models scored nothing against the rest)."""
+    grad_tol = Elo.GRAD_TOL if grad_tol is None else grad_tol
+    if anchor_model not in names:
+        raise ValueError(f"anchor model {anchor_model!r} is not registered")
+    idx = {m: i for i, m in enumerate(names)}
+    pairs = []  # (a, b, score of a, games) with the virtual draws in
+    for key, r in results.items():
+        a, b = key.split("__")
+        n = r["wins"] + r["draws"] + r["losses"]
+        if n <= 0 or a not in idx or b not in idx:
+            continue
+        pairs.append((idx[a], idx[b], r["wins"] + 0.5 * (r["draws"] + prior_draws), n + prior_draws))
+
+    def reach(edges):
+        reached, frontier = {idx[anchor_model]}, [idx[anchor_model]]
+        while frontier:
+            x = frontier.pop()
+            for u, w in edges:
+                if u == x and w not in reached:
+                    reached.add(w)
+                    frontier.append(w)
+        return reached
+
+    played = reach([e for a, b, _, _ in pairs for e in ((a, b), (b, a))])
+    missing = [m for m in names if idx[m] not in played]
+    if missing:
+        raise ValueError(f"no chain of played pairs connects {', '.join(missing)} to the anchor {anchor_model!r}")
+    # A finite maximum exists iff no group of models scored nothing at all against the rest (Ford 1957, draws as
+    # half wins): the graph "u scored against w" must be strongly connected.  Virtual draws make it so.
+    scored = [e for a, b, s, n in pairs for e in ([(a, b)] if s > 0 else []) + ([(b, a)] if n - s > 0 else [])]
+    if len(reach(scored)) < len(names) or len(reach([(w, u) for u, w in scored])) < len(names):
+        raise RuntimeError("the rating fit has no finite maximum: with prior_draws=0 a model (or a group of models) "
+                           "that scored nothing against the rest has no finite maximum-likelihood rating")
+    free = [i for i in range(len(names)) if i != idx[anchor_model]]
+    col = {i: k for k, i in enumerate(free)}
+    c = math.log(10.0) / Elo.ELO_CONSTANT
+    r = np.zeros(len(names), dtype=np.float64)
+    r[idx[anchor_model]] = float(anchor_elo)
+
+    def nll_grad_hess(r):
+        f, g, H = 0.0, np.zeros(len(free)), np.zeros((len(free), len(free)))
+        for a, b, s, n in pairs:
+            x = c * (r[a] - r[b])
+            # log E = -log1p(exp(-x)), log(1 - E) = -log1p(exp(x)), each in its stable form
+            le = -(math.log1p(math.exp(-x)) if x > 0 else -x + math.log1p(math.exp(x)))
+            l1 = -(math.log1p(math.exp(x)) if x < 0 else x + math.log1p(math.exp(-x)))
+            f -= s * le + (n - s) * l1
+            e = math.exp(le)
+            d, h = -(s - n * e) * c, n * e * (1.0 - e) * c * c
+            for u, sign in ((a, 1.0), (b, -1.0)):
+                if u in col:
+                    g[col[u]] += sign * d
+                    for w, sign2 in ((a, 1.0), (b, -1.0)):
+                        if w in col:
+                            H[col[u], col[w]] += sign * sign2 * h
+        return f, g, H
+
+    if not free:
+        return {anchor_model: float(anchor_elo)}
+    for _ in range(max_iter):
+        f, g, H = nll_grad_hess(r)
+        if np.max(np.abs(g)) < grad_tol:
+            break
+        lam = 1e-12 * max(1.0, float(np.trace(H)))
+        step = np.linalg.solve(H + lam * np.eye(len(free)), -g)
+        norm = float(np.max(np.abs(step)))
+        if norm > 4 * Elo.ELO_CONSTANT:  # the damping: no rating moves more than 1,600 points in one step
+            step *= 4 * Elo.ELO_CONSTANT / norm
+        t = 1.0
+        while True:
+            trial = r.copy()
+            trial[free] += t * step
+            if nll_grad_hess(trial)[0] <= f + 1e-13 * abs(f) or t < 1e-6:  # (rounding of f near the maximum)
+                break
+            t *= 0.5
+        r = trial
+    else:
+        raise RuntimeError(f"the rating fit did not reach a gradient below {grad_tol} in {max_iter} Newton steps")
+    return {m: float(r[idx[m]]) for m in names}
+
+
+class Elo:
+    """elo.py:15-137 on top of engine.LeagueEngine: compare_models plays all pairings in one arena."""
+
+    ELO_CONSTANT = 400
+    GRAD_TOL = 1e-10  # largest |d NLL / d rating| (per rating point) at which the fit stops
+
+    def __init__(self, model_database, seed=0, search_threads=4, dtype=torch.float16, device=None):
+        self.model_database = model_database
+        self.seed, self.search_threads, self.dtype, self.device = seed, search_threads, dtype, device
+        self.calls = 0
+
+    def compare_all(self, num_games=100):
+        return self.compare_models(*self.model_database.models().keys(), num_games=num_games)
+
+    def players(self, names):
+        """LeagueEngine player dicts of registered models."""
+        models, out = self.model_database.models(), []
+        for name in names:
+            e = models[name]
+            if e["policy"] == "MCTreeSearch":
+                kw = e["policy_kwargs"]
+                out.append(dict(network=self.model_database.network(name), iterations=int(kw.get("iterations", 100)),
+                                alpha=float(kw.get("alpha", 1)), strong_play=bool(kw.get("strong_play", False)),
+                                search_threads=self.search_threads))
+            else:
+                out.append(dict(kind="random" if e["policy"] == "Random" else "lookahead"))
+        return out
+
+    def compare_models(self, *names, num_games=100):
+        """Play num_games games (rounded up to an even number) between every two of `names`, all C(n, 2)
+        pairings in one league arena, and add the results to results.json under the reference's keys
+        (elo.py:45-71).  Returns the new results per key."""
+        from .arena import game_of_env
+        from .engine import LeagueEngine
+
+        names = list(names)
+        for n in names:
+            if "_" in n:
+                raise ValueError(f"model name {n!r} contains '_'")
+        if len(set(names)) != len(names) or len(names) < 2:
+            raise ValueError("compare_models needs at least two different models")
+        pairings = list(itertools.combinations(range(len(names)), 2))
+        eng = LeagueEngine(game_of_env(self.model_database.env), self.players(names), pairings,
+                           games_per_pairing=num_games, seed=self.seed + 7919 * self.calls,
+                           search_threads=self.search_threads, dtype=self.dtype, device=self.device)
+        self.calls += 1
+        try:
+            breakdowns = eng.play()
+        finally:
+            eng.close()
+        return self.accumulate([(names[i], names[j]) for i, j in pairings], breakdowns)
+
+    def accumulate(self, pairs, breakdowns):
+        """Add each pairing's breakdown ({"first": {...}, "second": {...}} in the first model's view) to
+        results.json."""
+        results, new = self.model_database.results(), {}
+        for (m1, m2), b in zip(pairs, breakdowns):
+            r = {s: b["first"][s] + b["second"][s] for s in ("wins", "draws", "losses")}
+            key, swap = result_key(m1, m2)
+            if swap:
+                r = {"wins": r["losses"], "draws": r["draws"], "losses": r["wins"]}
+            old = results.get(key, {"wins": 0, "draws": 0, "losses": 0})
+            results[key] = {s: int(old[s] + r[s]) for s in ("wins", "draws", "losses")}
+            new[key] = r
+        self.model_database.set_results(results)
+        return new
+
+    def calculate_elo(self, anchor_model="random", anchor_elo=0, prior_draws=1.0):
+        """Ratings of every registered model from results.json, the anchor fixed at anchor_elo; written to
+        elo.json and returned.  The reference's model (elo.py:176-191) solved as a deterministic full-batch
+        maximum-likelihood fit with `prior_draws` virtual draws per played pair (module docstring: a departure
+        from the reference's sampled SGD, whose 100-0 answers are where its step budget ran out).  Raises
+        ValueError if the played pairs do not connect every model to the anchor."""
+        names = list(self.model_database.models().keys())
+        ratings = fit_elo(names, self.model_database.results(), anchor_model, anchor_elo, prior_draws)
+        self.model_database.set_elos(ratings)
+        return ratings
+
+
+def main(argv=None):
+    import argparse
+
+    from .envs import Connect4Env, TicTacToeEnv
+
+    parser = argparse.ArgumentParser(description="rate registered models (the reference's main.py commands)")
+    parser.add_argument("command", choices=["compare_models", "calculate_elo"])
+    parser.add_argument("--dir", required=True, help="the ModelDatabase directory")
+    parser.add_argument("--g", dest="game", default="connect4", choices=["connect4", "tictactoe"])
+    parser.add_argument("--b", nargs="*", dest="board_size", help="board size: W H")
+    parser.add_argument("--p", nargs="*", help="players (default: every registered model)")
+    parser.add_argument("--games", type=int, default=100, help="games per pairing")
+    args = parser.parse_args(argv)
+    env = {"connect4": Connect4Env, "tictactoe": TicTacToeEnv}[args.game](*[int(x) for x in args.board_size or []])
+    elo = Elo(ModelDatabase(args.dir, env))
+    if args.command == "calculate_elo":
+        print(json.dumps(elo.calculate_elo(), indent=1, sort_keys=True))
+    elif args.p:
+        print(json.dumps(elo.compare_models(*args.p, num_games=args.games), indent=1, sort_keys=True))
+    else:
+        print(json.dumps(elo.compare_all(num_games=args.games), indent=1, sort_keys=True))
+
+
+if __name__ == "__main__":
+    main()

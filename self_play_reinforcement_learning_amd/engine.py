@@ -798,3 +798,203 @@ class LanedEngine:
 
     def check(self):
         self._each(lambda e: e.check())
+
+
+def league_schedule(pairings, games_per_pairing):
+    """The slot layout of a league: (g, [(first_slot, i, j), ...]).  Pairing p = (i, j) owns the consecutive
+    slots [p * g, (p + 1) * g), g = games_per_pairing rounded up to an even number, so (swap_sides = game id
+    odd = slot odd) each side moves first in half of a pairing's games."""
+    g = max(2, int(games_per_pairing) + (int(games_per_pairing) & 1))
+    return g, [(p * g, int(i), int(j)) for p, (i, j) in enumerate(pairings)]
+
+
+class LeagueEngine:
+    """All pairings of a model comparison in one arena (the GPU-native form of Elo.compare_models(*names),
+    games/algos/elo.py:73-100, which plays its pairings one SelfPlayScheduler.compare_models after another).
+
+    players: a list of dicts, each either {"network": ResidualTower (or anything make_evaluator takes),
+    "iterations", "alpha", "strong_play", "search_threads"} (the MCTreeSearch kwargs of that model's container)
+    or {"kind": "random" | "lookahead"} (hardcoded_players.py).  pairings: [(i, j), ...] indices into players.
+    Slot s of pairing (i, j) plays one game: tree 2s is player i, tree 2s + 1 player j, both in evaluate mode,
+    no Move records, no refill.  Each simulation step's leaf rows are partitioned by their tree's network
+    (Arena.league_route), every network evaluates its own segment, and the outputs return to arena-row order
+    (Arena.league_unroute) for the unchanged expand.  Every leaf is evaluated on its own (no leaf dedup, no
+    evaluation cache), as the reference's InferenceWorker does.  Players whose `network` is the same object
+    share an evaluator."""
+
+    KINDS = {"random": _lib.PLAYER_RANDOM, "lookahead": _lib.PLAYER_LOOKAHEAD,
+             "onesteplookahead": _lib.PLAYER_LOOKAHEAD}
+
+    def __init__(self, game, players, pairings, games_per_pairing=100, seed=0, search_threads=4,
+                 dtype=torch.float16, subsequence0=0, device=None, leaf_layout="nhwc", cpuct=4.0, x_noise=0.25,
+                 blocks_per_tree=0):
+        self.game = game
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.players = [dict(p) for p in players]
+        self.g, self.schedule = league_schedule(pairings, games_per_pairing)
+        for _, i, j in self.schedule:
+            if not (0 <= i < len(players) and 0 <= j < len(players)) or i == j:
+                raise ValueError(f"pairing ({i}, {j}) does not name two different players")
+        self.n_slots = n = self.g * len(self.schedule)
+        if n == 0:
+            raise ValueError("a league needs at least one pairing")
+        # one evaluator per distinct network object
+        self.evaluators, self.player_net, by_id = [], [], {}
+        K0 = max(1, int(search_threads))
+        for p in self.players:
+            if p.get("network") is None:
+                kind = str(p.get("kind", "")).lower()
+                if kind not in self.KINDS:
+                    raise ValueError(f"a player needs network= or kind= random / lookahead, got {p!r}")
+                self.player_net.append(-1)
+                continue
+            net = p["network"]
+            if id(net) not in by_id:
+                by_id[id(net)] = len(self.evaluators)
+                self.evaluators.append(make_evaluator(net, game, device=self.device, dtype=dtype,
+                                                      leaf_layout=leaf_layout))
+            self.player_net.append(by_id[id(net)])
+        if len(self.evaluators) > 32:
+            raise ValueError("a league arena holds at most 32 networks")
+        fmts = {(e.leaf_format, e.leaf_layout) for e in self.evaluators}
+        if len(fmts) > 1:
+            raise ValueError(f"all networks of a league must take the same leaf format, got {sorted(fmts)}")
+        fmt, layout = fmts.pop() if fmts else ("bf16", "nhwc")
+
+        def per_tree(key, default):
+            out = []
+            for _, i, j in self.schedule:
+                pair = [self.players[i].get(key, default), self.players[j].get(key, default)]
+                out += pair * self.g
+            return out
+
+        mcts = [p for p, k in zip(self.players, self.player_net) if k >= 0]
+        its = [int(p.get("iterations", 100)) for p in mcts] or [1]
+        ks = [max(1, int(p.get("search_threads", K0))) for p in mcts] or [K0]
+        self.iterations = max(its)
+        self.arena = a = Arena(game, n_trees=2 * n, n_games=n, iterations=self.iterations, seed=seed,
+                               subsequence0=subsequence0, evaluate=True, leaf_format=fmt, leaf_layout=layout,
+                               cpuct=cpuct, x_noise=x_noise, blocks_per_tree=blocks_per_tree, device=self.device,
+                               search_threads=max(ks))
+        self.search_threads = a.search_threads
+        self.select_steps = max([-(-int(p.get("iterations", 100)) // max(1, int(p.get("search_threads", K0))))
+                                 for p in mcts] or [0])
+        kind_of = [_lib.PLAYER_MCTS if k >= 0 else self.KINDS[str(p["kind"]).lower()]
+                   for p, k in zip(self.players, self.player_net)]
+        kinds, tree_net = [], []
+        for _, i, j in self.schedule:
+            kinds += [kind_of[i], kind_of[j]] * self.g
+            tree_net += [self.player_net[i], self.player_net[j]] * self.g
+        a.set_tree_search(alpha=[float(x) for x in per_tree("alpha", 1.0)],
+                          strong_play=[bool(x) for x in per_tree("strong_play", False)],
+                          search_threads=[min(a.search_threads, max(1, int(x))) for x in per_tree("search_threads", K0)])
+        a.set_tree_players(nets=None, kinds=kinds, budgets=[int(x) for x in per_tree("iterations", 100)])
+        a.games_set_record(False)
+        self.n_nets = len(self.evaluators)
+        if self.n_nets:
+            a.set_league(tree_net, self.n_nets)
+            for j, ev in enumerate(self.evaluators):
+                if hasattr(ev, "reserve"):
+                    ev.reserve(max(1, a.league_seg[j + 1] - a.league_seg[j]), self.device)
+        self.tree_net = tree_net
+        self.device_count = all(getattr(ev, "supports_device_count", False) for ev in self.evaluators)
+        self.launches = 0  # network launches (one per network with rows to take, per step)
+        self.plies = 0
+        self.games_done = 0
+        self.started = False
+
+    @torch.no_grad()
+    def _root_priors(self):
+        """games_start priors [n_slots, 2, A]: each network's evaluation of the empty board (MCTreeSearch.reset,
+        mcts.py:167-168); uniform for the hard-coded players, which never read them."""
+        a = self.arena
+        per_net = []
+        for ev in self.evaluators:
+            probs, _ = ev(ev.empty_root_input(a.W, a.H, a.device))
+            per_net.append(probs[0].float())
+        uniform = torch.full((a.A,), 1.0 / a.A, dtype=torch.float32, device=a.device)
+        rows = [per_net[k] if k >= 0 else uniform for k in self.tree_net]
+        return torch.stack(rows).reshape(self.n_slots, 2, a.A).contiguous()
+
+    def start(self):
+        a = self.arena
+        a.games_set_limit(self.n_slots)  # one game per slot, no refill
+        a.games_start(list(range(self.n_slots)), priors=self._root_priors())
+        self.started = True
+
+    def _eval_expand(self):
+        """Route the step's rows, one evaluation per network on its segment, unroute, expand."""
+        a = self.arena
+        if not self.n_nets:  # hard-coded players only: no tree sends a leaf
+            return
+        a.league_route()
+        outs = []
+        if self.device_count:
+            for j, ev in enumerate(self.evaluators):
+                cap = a.league_seg[j + 1] - a.league_seg[j]
+                if cap == 0:  # a network that owns no tree: nothing to launch, nothing read
+                    outs.append((a._probs, a._values))
+                    continue
+                outs.append(ev.forward_dev(a.routed_from(j), a.net_count_dev(j), cap))
+                self.launches += 1
+        else:
+            counts = a.net_counts()
+            for j, ev in enumerate(self.evaluators):
+                if counts[j] == 0:
+                    outs.append((a._probs, a._values))
+                    continue
+                outs.append(ev(a.routed_from(j)[:counts[j]]))
+                self.launches += 1
+        probs, values = a.league_unroute(outs)
+        a.expand(probs, values)
+
+    def ply(self):
+        """Advance every active game by one move; returns the number of games that finished."""
+        if not self.started:
+            self.start()
+        a = self.arena
+        a.games_begin_ply()
+        for step in range(self.select_steps):
+            if step == 0 or self.search_threads == 1:
+                a.select_async()
+            else:
+                a.leaf_rows_async()
+            self._eval_expand()
+        a.games_end_ply_async()
+        self._eval_expand()
+        finished, _ = a.games_finish_ply(refill=False)
+        self.games_done += finished
+        self.plies += 1
+        return finished
+
+    def play(self):
+        """Play every slot's game to its end.  Returns, per pairing, {"first": {wins, draws, losses}, "second":
+        {...}} in player i's view (parse_results' breakdown, self_play_parallel.py:302-327: "second" = the games
+        with swap_sides, where player j moved first)."""
+        limit = self.arena.cells + 2
+        while self.games_done < self.n_slots:
+            self.ply()
+            if self.plies > limit:
+                raise _lib.SpmctsError("league games did not finish within the board's cells")
+        self.check()
+        return self.results()
+
+    def results(self):
+        r = self.arena.games_results()
+        out = []
+        for first, _, _ in self.schedule:
+            b = {"first": dict(wins=0, draws=0, losses=0), "second": dict(wins=0, draws=0, losses=0)}
+            for s in range(first, first + self.g):
+                side = b["second" if r["swap"][s] else "first"]
+                side["wins" if r["result"][s] == 1 else ("draws" if r["result"][s] == 0 else "losses")] += 1
+            out.append(b)
+        return out
+
+    def counters(self):
+        return self.arena.counters()
+
+    def check(self):
+        self.arena.check()
+
+    def close(self):
+        self.arena.close()
