@@ -1,5 +1,5 @@
 // tower_common.h — what the three fused-trunk families share (namespace tower): the vector types, Ty (element
-// type and its MFMAs), the edge-layout tables, Cfg (one tile plan) and its two named forms, lds_b128, WBuf
+// type and its MFMAs), the edge-layout tables, Cfg (one tile plan) and its two named forms, one_opaque, lds_b128, WBuf
 // (weight ring loads), Nbr (neighbour rows), XLive (skipped edge tiles), phys_off, acc_init (the stems'
 // accumulator start) and head_layer (the 1x1 head convs that end every family's tile).
 //
@@ -53,6 +53,9 @@ struct Ty<__bf16> {
   static __device__ __forceinline__ f32x2 unpk(uint32_t x) {
     return f32x2{__uint_as_float(x << 16), __uint_as_float(x & 0xffff0000u)};
   }
+  // v + the pair packed in x.  `one` is unused: the widening is a shift or a mask, one operation already, and this
+  // chip has no mixed-precision FMA that reads a bf16 half
+  static __device__ __forceinline__ f32x2 add_pk(f32x2 v, uint32_t x, float one) { return v + unpk(x); }
   static __device__ __forceinline__ uint16_t from_bf16(__bf16 x) { return __builtin_bit_cast(uint16_t, x); }
 };
 template <>
@@ -73,6 +76,16 @@ struct Ty<_Float16> {
   }
   static __device__ __forceinline__ f32x2 unpk(uint32_t x) {
     return __builtin_convertvector(__builtin_bit_cast(f16x2, x), f32x2);
+  }
+  // v + the pair packed in x, one v_fma_mix_f32 per element: it reads the fp16 half in place, and x * 1 + v rounds
+  // once, as cvt + add does (the widening is exact).  `one` is 1.0f in a register the compiler cannot see through
+  // (one_opaque): with a literal 1 it folds the fma back into cvt + add.
+  static __device__ __forceinline__ f32x2 add_pk(f32x2 v, uint32_t x, float one) {
+    const f16x2 h = __builtin_bit_cast(f16x2, x);
+    float a = __builtin_fmaf((float)h[0], one, v[0]), b = __builtin_fmaf((float)h[1], one, v[1]);
+    asm("" : "+v"(a));  // scalar results: packed into one v_pk_fma_f32, the pair would need its two cvts back
+    asm("" : "+v"(b));
+    return f32x2{a, b};
   }
   static __device__ __forceinline__ uint16_t from_bf16(__bf16 x) {
     return __builtin_bit_cast(uint16_t, (_Float16)(float)x);
@@ -156,6 +169,13 @@ using BoardMajor32 = Cfg<C, ROWS, W, H, C / 64, 4, 4, 1, false, false, E>;
 // 6-board Connect4 edge tiles on 16x16x32, weight ring 2 deep: two buffers (tower_m16.h) or one (tower_wide16.h).
 template <int C, bool ONEBUF, class E>
 using Edge16 = Cfg<C, 256, 7, 6, C / 64, 4, 2, 1, true, true, E, ONEBUF, true>;
+
+// 1.0f as a wave-uniform value the compiler treats as unknown (Ty::add_pk's multiplier)
+__device__ __forceinline__ float one_opaque() {
+  float one = 1.0f;
+  asm("" : "+s"(one));
+  return one;
+}
 
 __device__ __forceinline__ bf16x8 lds_b128(const char *p) { return *(const bf16x8 *)p; }
 

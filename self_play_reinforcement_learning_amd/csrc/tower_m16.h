@@ -158,7 +158,7 @@ __device__ __forceinline__ void conv_tap(const char *src, const Nbr<K> &nb, f32x
 // out = relu(acc + bias (+ the block input at the same physical positions, RESID)), into dst.
 template <class K, bool RESID>
 __device__ __forceinline__ void epilogue(const f32x4 (&acc)[MM<K>][K::NT][2], char *dst, const float4 (&bv)[MM<K>],
-                                         int cg, int mg, int q, int rb) {
+                                         int cg, int mg, int q, int rb, float one) {
   constexpr int NM = MM<K>, NU = NM / 2;  // the run: NU 16-byte pieces
 #pragma unroll
   for (int t = 0; t < K::NT; ++t) {
@@ -179,18 +179,14 @@ __device__ __forceinline__ void epilogue(const f32x4 (&acc)[MM<K>][K::NT][2], ch
 #pragma unroll
       for (int mm = 0; mm < NM; ++mm) {
         // physical 4 mm + r within the run: output channel 16 mm + 4 q + r
-        float v0 = acc[mm][t][h][0] + bv[mm].x, v1 = acc[mm][t][h][1] + bv[mm].y;
-        float v2 = acc[mm][t][h][2] + bv[mm].z, v3 = acc[mm][t][h][3] + bv[mm].w;
-        if constexpr (RESID) {
-          const f32x2 x0 = K::unpk(((const uint32_t *)&res[h][mm >> 1])[2 * (mm & 1)]);
-          const f32x2 x1 = K::unpk(((const uint32_t *)&res[h][mm >> 1])[2 * (mm & 1) + 1]);
-          v0 += x0[0];
-          v1 += x0[1];
-          v2 += x1[0];
-          v3 += x1[1];
+        f32x2 v01 = f32x2{acc[mm][t][h][0], acc[mm][t][h][1]} + f32x2{bv[mm].x, bv[mm].y};
+        f32x2 v23 = f32x2{acc[mm][t][h][2], acc[mm][t][h][3]} + f32x2{bv[mm].z, bv[mm].w};
+        if constexpr (RESID) {  // (acc + bias) + the block input
+          v01 = K::add_pk(v01, ((const uint32_t *)&res[h][mm >> 1])[2 * (mm & 1)], one);
+          v23 = K::add_pk(v23, ((const uint32_t *)&res[h][mm >> 1])[2 * (mm & 1) + 1], one);
         }
-        o[2 * mm] = K::relu_pk(f32x2{v0, v1});
-        o[2 * mm + 1] = K::relu_pk(f32x2{v2, v3});
+        o[2 * mm] = K::relu_pk(v01);
+        o[2 * mm + 1] = K::relu_pk(v23);
       }
 #pragma unroll
       for (int u = 0; u < NU; ++u) *(uint4 *)(p + 16 * u) = make_uint4(o[4 * u], o[4 * u + 1], o[4 * u + 2], o[4 * u + 3]);
@@ -198,14 +194,16 @@ __device__ __forceinline__ void epilogue(const f32x4 (&acc)[MM<K>][K::NT][2], ch
   }
 }
 
+// One 3x3 conv layer of the wave's tiles.  lds: the start of LDS; qoff: the lane's 16-byte quarter plus the source
+// buffer's base (tile); one: Ty::add_pk's multiplier.
 template <class K, int KK32, int DEPTH, bool RESID, int MG_>
-__device__ __forceinline__ void conv_layer(const char *src, char *dst, const Nbr<K> &nb, bf16x8 (&a)[DEPTH][MM<K>],
-                                           const float *bias, int cg, int lane, const WBuf &wb, uint32_t wl_off,
-                                           uint32_t wn_off) {
+__device__ __forceinline__ void conv_layer(const char *lds, int qoff, char *dst, const Nbr<K> &nb,
+                                           bf16x8 (&a)[DEPTH][MM<K>], const float *bias, int cg, int lane,
+                                           const WBuf &wb, uint32_t wl_off, uint32_t wn_off, float one) {
   using X = XLive<K, MG_>;
   constexpr int NM = MM<K>;
   static_assert(KK32 % DEPTH == 0, "ring slot must be a compile-time function of k");
-  const int q = lane >> 4, rb = lane_row(lane & 15), qoff = 16 * q;
+  const int q = lane >> 4, rb = lane_row(lane & 15);
   float4 bv[NM];  // the epilogue's bias, fetched now (its latency hides under the k-loop)
 #pragma unroll
   for (int mm = 0; mm < NM; ++mm) bv[mm] = *(const float4 *)(bias + 16 * (NM * cg + mm) + 4 * q);
@@ -223,13 +221,13 @@ __device__ __forceinline__ void conv_layer(const char *src, char *dst, const Nbr
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         off_cur[t][h] = src_row(nb, MG_, t, h, rb, 0) * K::RS + qoff;
-        bc[t][h] = lds_b128(src + off_cur[t][h]);
+        bc[t][h] = lds_b128(lds + off_cur[t][h]);
       }
     }
-#define TAP16(T) conv_tap<K, KK32, DEPTH, MG_, T>(src, nb, acc, bc, bn, off_cur, off_nxt, a, qoff, rb, wb, wl_off, wn_off)
+#define TAP16(T) conv_tap<K, KK32, DEPTH, MG_, T>(lds, nb, acc, bc, bn, off_cur, off_nxt, a, qoff, rb, wb, wl_off, wn_off)
   TAP16(0); TAP16(1); TAP16(2); TAP16(3); TAP16(4); TAP16(5); TAP16(6); TAP16(7); TAP16(8);
 #undef TAP16
-  epilogue<K, RESID>(acc, dst, bv, cg, MG_, q, rb);
+  epilogue<K, RESID>(acc, dst, bv, cg, MG_, q, rb, one);
 }
 
 // The stem's epilogue (32x32x16 accumulators, bias already in them): lane's output channels
@@ -336,20 +334,32 @@ __device__ __forceinline__ void tile(char *smem, const __bf16 *planes, int batch
   wb.voff = lane * 16;
   const int cg_u = __builtin_amdgcn_readfirstlane(cg);
   const uint32_t ct0_off = (uint32_t)(STEM + (size_t)(NM * cg_u) * LSTEPS * 64) * 16u;
+  // A layer's operand offsets are byte addresses from the start of LDS with its source buffer's base already in
+  // them (added once per row offset, through qoff: conv_layer), so every read of a k-step is base register +
+  // immediate (k * 64) whichever buffer the layer reads.  Left to itself the compiler folds Y's base (beyond the
+  // 16-bit ds_read immediate) into each k-step's constant and pays one v_add_u32 per read in every second layer;
+  // the empty asm, once per tile, keeps the sum opaque.
+  const int qoff_x = 16 * (lane >> 4);
+  int qoff_y = qoff_x + K::BUF;
+  asm("" : "+v"(qoff_y));
+  const float one = one_opaque();  // the residual add's multiplier (Ty::add_pk)
+#define LAYER16(RESID, MG_, QOFF, DST) \
+  conv_layer<K, KK32, DEPTH, RESID, MG_>(smem, QOFF, DST, nb, ring, b, cg, lane, wb, wl_off, wn_off, one)
   for (int L = 0; L < n_convs; ++L) {
     const uint32_t wl_off = ct0_off + (uint32_t)((size_t)L * LAYER * 16u);
     const uint32_t wn_off = L + 1 == n_convs ? wl_off : wl_off + (uint32_t)(LAYER * 16u);
     const bool even = (L & 1) == 0;
     if (wave / K::CG == 0) {
-      if (even) conv_layer<K, KK32, DEPTH, false, 0>(X, Y, nb, ring, b, cg, lane, wb, wl_off, wn_off);
-      else conv_layer<K, KK32, DEPTH, true, 0>(Y, X, nb, ring, b, cg, lane, wb, wl_off, wn_off);
+      if (even) LAYER16(false, 0, qoff_x, Y);
+      else LAYER16(true, 0, qoff_y, X);
     } else {
-      if (even) conv_layer<K, KK32, DEPTH, false, 1>(X, Y, nb, ring, b, cg, lane, wb, wl_off, wn_off);
-      else conv_layer<K, KK32, DEPTH, true, 1>(Y, X, nb, ring, b, cg, lane, wb, wl_off, wn_off);
+      if (even) LAYER16(false, 1, qoff_x, Y);
+      else LAYER16(true, 1, qoff_y, X);
     }
     b += K::C;
     __syncthreads();
   }
+#undef LAYER16
   head_layer<K>(X, wblk + (size_t)n_convs * LAYER, b, out, board0, batch, wave, lane);
 }
 
