@@ -256,6 +256,14 @@ int spmcts_leaf_trees(spmcts_arena *h, int32_t *trees_dev, spmcts_stream stream)
 /* (sync) root statistics of one tree: children n/w/p (A each), root n/w, player, board */
 int spmcts_root_stats(spmcts_arena *h, int32_t tree, int32_t *child_n, double *child_w, float *child_p,
                       int32_t *root_n, double *root_w, int32_t *root_player, int8_t *board /*[W*H]*/);
+/* spmcts_root_stats of the n listed trees into device arrays, with no host synchronisation: the root's
+ * children's visit counts, w and priors (the n, w, p that _play reads, mcts.py:272-277; [n][A] each), the
+ * root's own n and w (its q, mcts.py:59-62), the player to move ([n] each) and the root board (int8 [n][W*H],
+ * tree frame).  The values are those of spmcts_root_stats, bit for bit; any output may be NULL.  A tree id
+ * outside the arena raises SPMCTS_ERR_STATE. */
+int spmcts_root_stats_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n, int32_t *child_n_dev,
+                            double *child_w_dev, float *child_p_dev, int32_t *root_n_dev, double *root_w_dev,
+                            int8_t *root_player_dev, int8_t *boards_dev, spmcts_stream stream);
 
 /* ---- games-level API (SelfPlayer.play_episode state machine) -------------- */
 /* Start games in the listed slots (selfplayworker.py:172-179): both trees reset,
@@ -288,6 +296,29 @@ int spmcts_games_state(spmcts_arena *h, uint8_t *active, int32_t *ply, uint8_t *
  * values after its game is finished until another game starts in it, so an arena that plays one game per slot
  * (no refill) reads every game's outcome here (the per-pairing results of compare_models, elo.py:49-71). */
 int spmcts_games_results(spmcts_arena *h, int8_t *result, uint8_t *swap, int32_t *ply, uint8_t *state);
+
+/* ---- opening book: games that start from given move sequences ------------------------------------------------ */
+/* An opening is a sequence of actions m[0..L) from the empty board, m[0] played by whoever moves first in the
+ * game.  While ply < L the game is in its book: the ply is SelfPlayer.play_move (selfplayworker.py:221-224)
+ * applied to m[ply] -- the same env.step and the same play_action / _set_node on both trees (mcts.py:188-209),
+ * expansion rows and backup included -- but nobody searches: no root noise, no random number, no tree in the
+ * active set, no Move record (the reference records in _play only, mcts.py:272-299).  From ply L on the game
+ * runs as without a book.  Game id i plays opening ((i mod id_period) >> 1) mod n_openings (id_period 0: no
+ * modulus), so ids 2k and 2k + 1 play one opening with and without swap_sides (self_play_parallel.py:237);
+ * refilled games take theirs from their new id.
+ *
+ * (sync) host arrays: moves uint8 [n_openings][max_len], lens int32 [n_openings].  n_openings <= 65536 (0 turns
+ * the book off), max_len < W * H, id_period even.  Every sequence is validated on the host with the board rules
+ * of spmcts_env_step_host: an illegal move, or one that ends the game, returns -3 and spmcts_last_error names
+ * the opening and the ply ("opening I ply P: ...").  Refused (-4) while any game slot is active.  On the device
+ * a book move that is illegal or ends the game raises SPMCTS_ERR_ACTION / SPMCTS_ERR_STATE. */
+int spmcts_games_set_openings(spmcts_arena *h, const uint8_t *moves, const int32_t *lens, int32_t n_openings,
+                              int32_t max_len, int32_t id_period);
+/* The validation of spmcts_games_set_openings alone (host only: no arena, no GPU), same return and message. */
+int spmcts_openings_validate(int32_t game, int32_t width, int32_t height, const uint8_t *moves, const int32_t *lens,
+                             int32_t n_openings, int32_t max_len);
+/* (sync) host int32 [n_games]: the opening each slot's game plays; -1 for an idle slot or without a book. */
+int spmcts_games_openings(spmcts_arena *h, int32_t *opening_of_slot);
 
 /* ---- league: N networks in one arena (Elo.compare_models(*names), games/algos/elo.py:73-100) ---------------- */
 /* A league arena is a single-network arena (spmcts_set_tree_players nets all 0) whose trees send their leaves

@@ -10,7 +10,8 @@ Public API mirrors the reference:
     Connect4Env, TicTacToeEnv             (games/connect4, games/tictactoe)
     OneStepLookahead, Random              (games/general/hardcoded_players.py)
     Elo, ModelDatabase                    (games/algos/elo.py, games/algos/model_database.py)
-plus the arena itself: Arena, SelfPlayEngine, LanedEngine, LeagueEngine, DeviceTableNet.
+plus the arena itself: Arena, SelfPlayEngine, LanedEngine, LeagueEngine, DeviceTableNet, and what the reference
+has no form of: opening books (openings.py: enumerate_openings, validate_openings) and analyse_positions.
 """
 from .base_model import BasePlayer, ModelContainer, Policy, TrainableModel  # noqa: F401
 from .memory import Memory  # noqa: F401
@@ -27,6 +28,9 @@ _LAZY = {
     "make_evaluator": ".evaluator",
     "MCTreeSearch": ".mcts",
     "Move": ".mcts",
+    "analyse_positions": ".mcts",
+    "enumerate_openings": ".openings",
+    "validate_openings": ".openings",
     "SelfPlayScheduler": ".self_play_parallel",
     "Connect4Env": ".envs",
     "TicTacToeEnv": ".envs",

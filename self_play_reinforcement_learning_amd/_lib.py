@@ -119,6 +119,10 @@ _SIGS = {
     "spmcts_export_moves": [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P],
     "spmcts_games_state": [_P, _P, _P, _P, _P],
     "spmcts_games_results": [_P, _P, _P, _P, _P],
+    "spmcts_games_set_openings": [_P, _P, _P, _I32, _I32, _I32],
+    "spmcts_openings_validate": [_I32, _I32, _I32, _P, _P, _I32, _I32],
+    "spmcts_games_openings": [_P, _P],
+    "spmcts_root_stats_batch": [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
     "spmcts_set_league": [_P, _P, _I32],
     "spmcts_league_segments": [_P, _P],
     "spmcts_league_route": [_P, _P, _P, _I32, _P, _P, _P],

@@ -378,7 +378,47 @@ class Arena:
         return dict(child_n=list(cn), child_w=list(cw), child_p=list(cp), root_n=rn.value, root_w=rw.value,
                     root_player=rp.value, board=np.array(list(board), dtype=np.int8).reshape(self.W, self.H))
 
+    def root_stats_batch(self, trees):
+        """root_stats of the listed trees (a list or a device int32 tensor) as device tensors, queued on the
+        current stream without a host synchronisation (include/spmcts.h spmcts_root_stats_batch): child_n int32
+        [n, A], child_w float64 [n, A], child_p float32 [n, A], root_n int32 [n], root_w float64 [n], root_player
+        int8 [n], board int8 [n, W, H]."""
+        t = trees.to(self.device, torch.int32).contiguous() if torch.is_tensor(trees) else self._dev_i32(trees)
+        n, A, dev = int(t.numel()), self.A, self.device
+        out = dict(child_n=torch.zeros((n, A), dtype=torch.int32, device=dev),
+                   child_w=torch.zeros((n, A), dtype=torch.float64, device=dev),
+                   child_p=torch.zeros((n, A), dtype=torch.float32, device=dev),
+                   root_n=torch.zeros(n, dtype=torch.int32, device=dev),
+                   root_w=torch.zeros(n, dtype=torch.float64, device=dev),
+                   root_player=torch.zeros(n, dtype=torch.int8, device=dev),
+                   board=torch.zeros((n, self.W, self.H), dtype=torch.int8, device=dev))
+        call("spmcts_root_stats_batch", self.h, ptr(t), n, ptr(out["child_n"]), ptr(out["child_w"]),
+             ptr(out["child_p"]), ptr(out["root_n"]), ptr(out["root_w"]), ptr(out["root_player"]), ptr(out["board"]),
+             _stream())
+        self._stats_trees = t  # alive until the kernel has run
+        return out
+
     # ------------------------------------------------------------------ games API
+    def games_set_openings(self, openings, id_period=0):
+        """The arena's opening book (include/spmcts.h spmcts_games_set_openings): `openings` a list of move
+        lists from the empty board; game id i plays opening ((i mod id_period) >> 1) mod len(openings), its book
+        plies without a search.  None or [] turns the book off.  Raises SpmctsError for a sequence with an illegal
+        or game-ending move ("opening I ply P: ..."), an odd id_period, or while a game is active."""
+        from .openings import pack_openings
+
+        moves, lens, max_len = pack_openings(openings or [])
+        torch.cuda.current_stream().synchronize()
+        call("spmcts_games_set_openings", self.h, moves.ctypes.data_as(ctypes.c_void_p),
+             lens.ctypes.data_as(ctypes.c_void_p), len(lens), max_len, int(id_period))
+        self.n_openings = len(lens)
+
+    def games_openings(self):
+        """Opening index of each slot's game (sync; -1: an idle slot, or no book)."""
+        out = np.zeros(max(self.n_games, 1), dtype=np.int32)
+        torch.cuda.current_stream().synchronize()
+        call("spmcts_games_openings", self.h, out.ctypes.data_as(ctypes.c_void_p))
+        return out[:self.n_games]
+
     def games_start(self, slots, priors=None):
         """priors: optional float32 [n, 2, A] (policy tree, opponent tree) root priors per game."""
         s = self._dev_i32(slots)

@@ -1,4 +1,4 @@
-// arena_games.h — the SelfPlayer game state machine and the export kernels.
+// arena_games.h — the SelfPlayer game state machine (opening book plies included), k_root_stats_batch and the export kernels.
 // Included by spmcts.hip after arena_expand.h: needs reset_tree, set_node and the search helpers.
 // ----------------------------------------------------------------------------
 // games: SelfPlayer.play_episode state machine (selfplayworker.py:164-224)
@@ -18,7 +18,17 @@ __device__ void start_game(const View &v, int g, int64_t id, const float *priors
   // policy.reset(-1 if swap else 1), opposing.reset(1 if swap else -1)  (:175-176)
   reset_tree<G>(v, 2 * g, swap ? -1 : 1, priors ? priors : v.root_prior + 16 * v.tnet[2 * g]);
   reset_tree<G>(v, 2 * g + 1, swap ? 1 : -1, priors ? priors + G::A : v.root_prior + 16 * v.tnet[2 * g + 1]);
+  if (v.book_n) {  // ids 2k and 2k + 1 play the same opening, once per colour
+    const int64_t i = v.book_period ? id % v.book_period : id;
+    const int o = (int)((i >> 1) % v.book_n);
+    v.gopen[g] = o;
+    v.gbook[g] = v.book_lens[o];
+  }
 }
+
+// The game plays a move of its opening this ply (SelfPlayer.play_move, selfplayworker.py:221-224, on a given
+// action): no search, no noise, no random number, no Move record.
+__device__ __forceinline__ bool in_book(const View &v, int g) { return v.book_n && v.gply[g] < v.gbook[g]; }
 
 template <class G>
 __global__ void k_games_start(View v, const int32_t *slots, const float *priors, int n) {
@@ -39,6 +49,10 @@ __global__ void k_games_begin_ply(View v) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= v.G) return;
   if (v.gstate[g] != GS_ACTIVE) {
+    v.active[g] = -1;
+    return;
+  }
+  if (in_book(v, g)) {  // a book ply: nobody searches
     v.active[g] = -1;
     return;
   }
@@ -105,7 +119,10 @@ __global__ void k_games_end_ply(View v) {
   float pr[G::A];
   PlayOut o{0, false, 0.0, 0};
   const int kind = v.tkind[tree];
-  if (kind == SPMCTS_PLAYER_MCTS) {
+  const bool book = in_book(v, g);
+  if (book) {
+    o.action = v.book_moves[(size_t)v.gopen[g] * v.book_len + v.gply[g]];
+  } else if (kind == SPMCTS_PLAYER_MCTS) {
     o = play_move_choice<G>(v, tree, 1.0, pr);
   } else {
     const Board envb = mover == 0 ? Board{v.gpos[g], v.gneg[g]} : Board{v.gneg[g], v.gpos[g]};
@@ -127,11 +144,14 @@ __global__ void k_games_end_ply(View v) {
   const int p_env = mover == 0 ? 1 : -1;
   Board gb{v.gpos[g], v.gneg[g]};
   int rew = 0, done = 0;
+  // a book move is held to the host validation's rule (an occupied TicTacToe cell is a silent no-op of step)
+  if (book && (o.action >= G::A || !((legal_mask<G>(gb) >> o.action) & 1u))) set_err(v, SPMCTS_ERR_ACTION);
   const int st = step<G>(gb, o.action, p_env, &rew, &done);
   if (st != STEP_OK) set_err(v, SPMCTS_ERR_ACTION);
   v.gpos[g] = gb.pos;
   v.gneg[g] = gb.neg;
   v.gply[g] += 1;
+  if (done && book) set_err(v, SPMCTS_ERR_STATE);  // host validation keeps a book move from ending the game
   if (done) {
     v.gstate[g] = GS_DONE;
     v.gresult[g] = (int8_t)(rew * p_env);  // r = r * player (:218)
@@ -240,6 +260,40 @@ __global__ void k_games_finish_apply(View v) {
     start_game<G>(v, g, started + fin_idx, nullptr);
   } else {
     v.gstate[g] = GS_IDLE;
+  }
+}
+
+// Root statistics of n listed trees, the values of spmcts_root_stats, with no host synchronisation: one
+// APAD-lane group per tree (lane j: child j; lane 0: the root's own fields; the board's cells strided).
+template <class G>
+__global__ void k_root_stats_batch(View v, const int32_t *trees, int n, int32_t *child_n, double *child_w,
+                                   float *child_p, int32_t *root_n, double *root_w, int8_t *root_player, int8_t *boards) {
+  constexpr int P = G::APAD;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = t / P, j = t % P;
+  if (i >= n) return;
+  const int tree = trees[i];
+  if (tree < 0 || tree >= v.T) {
+    if (j == 0) set_err(v, SPMCTS_ERR_STATE);
+    return;
+  }
+  const size_t nb = nbase<G>(v, tree);
+  const int root = v.root[tree];
+  const int cb = nd_c<P>(v, nb + root);
+  if (j < G::A) {
+    const size_t c = nb + (size_t)(cb >= 0 ? cb : 0) * P + j, o = (size_t)i * G::A + j;
+    if (child_n) child_n[o] = cb >= 0 ? nd_n<P>(v, c) : 0;
+    if (child_w) child_w[o] = cb >= 0 ? nd_w<P>(v, c) : 0.0;
+    if (child_p) child_p[o] = cb >= 0 ? nd_p<P>(v, c) : 0.f;
+  }
+  if (j == 0) {
+    if (root_n) root_n[i] = nd_n<P>(v, nb + root);
+    if (root_w) root_w[i] = nd_w<P>(v, nb + root);
+    if (root_player) root_player[i] = v.rplayer[tree];
+  }
+  if (boards) {
+    const Board b{v.rpos[tree], v.rneg[tree]};
+    for (int c = j; c < G::CELLS; c += P) boards[(size_t)i * G::CELLS + c] = cell_value<G>(b, c / G::H, c % G::H);
   }
 }
 

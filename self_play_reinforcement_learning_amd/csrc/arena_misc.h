@@ -113,6 +113,8 @@ __global__ void k_games_init(View v) {
   v.gstate[g] = GS_IDLE;
   v.mv_count[2 * g] = 0;
   v.mv_count[2 * g + 1] = 0;
+  v.gopen[g] = -1;  // no opening book (spmcts_games_set_openings)
+  v.gbook[g] = 0;
 }
 
 __global__ void k_set_tape(View v, const int64_t *offsets) {

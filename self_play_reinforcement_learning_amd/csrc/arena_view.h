@@ -116,7 +116,18 @@ struct View {
   int32_t seg1;      // first leaf row of network 1 (= number of network-0 trees)
   int32_t record;    // games mode: keep Move records (play_episode update=True)
   int32_t sim;       // index of the current simulation within the search (by value per launch)
+  // opening book (spmcts_games_set_openings): book_n openings of book_len bytes each (book_n = 0: off, the one
+  // scalar the game kernels branch on), game id i plays opening ((i mod book_period) >> 1) mod book_n
+  // (book_period 0: no modulus).  A game is in its book while gply < gbook: its ply's action is
+  // book_moves[gopen * book_len + gply], nobody searches and no random number is drawn
+  int32_t book_n, book_len, book_period;
+  uint8_t *book_moves;  // [BOOK_MAX_OPENINGS][cells - 1] capacity, rows of book_len
+  int32_t *book_lens;   // [BOOK_MAX_OPENINGS]
+  int32_t *gopen;       // [G] the game's opening (-1: none)
+  int32_t *gbook;       // [G] that opening's length (0: none)
 };
+
+enum { BOOK_MAX_OPENINGS = 65536 };
 
 // Node store.  A child block (the A children of one expanded node, P = APAD slots) is ONE contiguous
 // record of 32 * P bytes: n i32[P] | vl i32[P] | child-block i32[P] | p f32[P] | w f64[P] | f64 flag

@@ -31,7 +31,7 @@
 //   arena_select.h  resets and noise, k_compact, DPP reductions, k_select, the threaded sim and slot fill
 //   arena_rows.h    leaf dedup, evaluation cache, peer push, k_scan_need, k_encode
 //   arena_expand.h  k_expand, threaded expand and select (one slot-cycle walk), _play, k_search_end, set_node, k_play_action
-//   arena_games.h   game state machine, export
+//   arena_games.h   game state machine (opening book plies included), k_root_stats_batch, export
 //   arena_misc.h    k_env_step, k_table_net, k_copy_probe, the init kernels
 //   arena_league.h  league routing: a step's rows partitioned by their tree's network, and back
 //
@@ -284,6 +284,11 @@ static void plan_arena(spmcts_arena *h, Plan &pl) {
   pl.add(&v.talpha, T);
   pl.add(&v.tstrong, T);
   pl.add(&v.tK, T);
+  // the opening book at its limits (spmcts_games_set_openings): BOOK_MAX_OPENINGS sequences shorter than the board
+  pl.add(&v.book_moves, G ? (size_t)BOOK_MAX_OPENINGS * (h->cells - 1) : 1);
+  pl.add(&v.book_lens, G ? (size_t)BOOK_MAX_OPENINGS : 1);
+  pl.add(&v.gopen, G);
+  pl.add(&v.gbook, G);
 }
 
 static int setup_view(spmcts_arena *h, const spmcts_config *cfg) {
@@ -947,6 +952,89 @@ int spmcts_games_results(spmcts_arena *h, int8_t *result, uint8_t *swap, int32_t
   if (ply) HIP_TRY(hipMemcpy(ply, h->v.gply, 4 * G, hipMemcpyDeviceToHost));
   if (state) HIP_TRY(hipMemcpy(state, h->v.gstate, G, hipMemcpyDeviceToHost));
   return 0;
+}
+
+// ---- opening book ---------------------------------------------------------
+int spmcts_openings_validate(int32_t game, int32_t width, int32_t height, const uint8_t *moves, const int32_t *lens,
+                             int32_t n_openings, int32_t max_len) {
+  if (n_openings < 0 || n_openings > BOOK_MAX_OPENINGS) return fail(-3, "openings: 0 .. 65536 sequences");
+  if (n_openings == 0) return 0;
+  if (!moves || !lens) return fail(-1, "null argument");
+  return with_game(game, width, height, [&](auto g) {
+    using G = decltype(g);
+    if (max_len < 0 || max_len >= G::CELLS) return fail(-3, "openings: max_len must be below width * height");
+    char buf[160];
+    for (int i = 0; i < n_openings; ++i) {
+      if (lens[i] < 0 || lens[i] > max_len) {
+        snprintf(buf, sizeof(buf), "opening %d: length %d outside [0, max_len = %d]", i, lens[i], max_len);
+        return fail(-3, buf);
+      }
+      Board b{0, 0};
+      int player = 1;  // legality and the game's end do not depend on who moves first
+      for (int p = 0; p < lens[i]; ++p, player = -player) {
+        const int a = moves[(size_t)i * max_len + p];
+        int r = 0, d = 0;
+        if (a >= G::A || !((legal_mask<G>(b) >> a) & 1u) || step<G>(b, a, player, &r, &d) != STEP_OK) {
+          snprintf(buf, sizeof(buf), "opening %d ply %d: illegal move %d", i, p, a);
+          return fail(-3, buf);
+        }
+        if (d) {
+          snprintf(buf, sizeof(buf), "opening %d ply %d: move %d ends the game", i, p, a);
+          return fail(-3, buf);
+        }
+      }
+    }
+    return 0;
+  });
+}
+
+int spmcts_games_set_openings(spmcts_arena *h, const uint8_t *moves, const int32_t *lens, int32_t n_openings,
+                              int32_t max_len, int32_t id_period) {
+  if (!h) return fail(-1, "null arena");
+  if (h->v.G <= 0) return fail(-4, "arena has no game slots");
+  if (id_period < 0 || (id_period & 1)) return fail(-3, "openings: id_period must be even (0 = no modulus)");
+  TRY(spmcts_openings_validate(h->cfg.game, h->W, h->H, moves, lens, n_openings, max_len));
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t G = h->v.G;
+  std::vector<uint8_t> st(G);
+  HIP_TRY(hipMemcpy(st.data(), h->v.gstate, G, hipMemcpyDeviceToHost));
+  for (uint8_t s : st)
+    if (s != GS_IDLE) return fail(-4, "openings cannot change while a game is active");
+  View &v = h->v;
+  HIP_TRY(hipMemset(v.gopen, 0xff, 4 * G));  // -1: no opening
+  HIP_TRY(hipMemset(v.gbook, 0, 4 * G));
+  v.book_n = v.book_len = v.book_period = 0;
+  if (n_openings == 0) return 0;
+  if (max_len > 0) HIP_TRY(hipMemcpy(v.book_moves, moves, (size_t)n_openings * max_len, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(v.book_lens, lens, 4 * (size_t)n_openings, hipMemcpyHostToDevice));
+  v.book_n = n_openings;
+  v.book_len = max_len;
+  v.book_period = id_period;
+  return 0;
+}
+
+int spmcts_games_openings(spmcts_arena *h, int32_t *opening_of_slot) {
+  if (!h || !opening_of_slot) return fail(-1, "null argument");
+  const size_t G = h->v.G;
+  if (!G) return 0;
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<uint8_t> st(G);
+  HIP_TRY(hipMemcpy(st.data(), h->v.gstate, G, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(opening_of_slot, h->v.gopen, 4 * G, hipMemcpyDeviceToHost));
+  for (size_t g = 0; g < G; ++g)
+    if (!h->v.book_n || st[g] == GS_IDLE) opening_of_slot[g] = -1;
+  return 0;
+}
+
+int spmcts_root_stats_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n, int32_t *child_n_dev,
+                            double *child_w_dev, float *child_p_dev, int32_t *root_n_dev, double *root_w_dev,
+                            int8_t *root_player_dev, int8_t *boards_dev, spmcts_stream stream) {
+  if (!h) return fail(-1, "null arena");
+  if (n <= 0) return 0;
+  if (!trees_dev) return fail(-1, "null argument");
+  return LAUNCH(h, k_root_stats_batch, (long long)n * h->P, 256, (hipStream_t)stream, h->v, trees_dev, n, child_n_dev,
+                child_w_dev, child_p_dev, root_n_dev, root_w_dev, root_player_dev, boards_dev);
 }
 
 // ---- league ---------------------------------------------------------------

@@ -258,8 +258,8 @@ class Elo:
         self.seed, self.search_threads, self.dtype, self.device = seed, search_threads, dtype, device
         self.calls = 0
 
-    def compare_all(self, num_games=100):
-        return self.compare_models(*self.model_database.models().keys(), num_games=num_games)
+    def compare_all(self, num_games=100, openings=None):
+        return self.compare_models(*self.model_database.models().keys(), num_games=num_games, openings=openings)
 
     def players(self, names):
         """LeagueEngine player dicts of registered models."""
@@ -275,12 +275,16 @@ class Elo:
                 out.append(dict(kind="random" if e["policy"] == "Random" else "lookahead"))
         return out
 
-    def compare_models(self, *names, num_games=100):
+    def compare_models(self, *names, num_games=100, openings=None):
         """Play num_games games (rounded up to an even number) between every two of `names`, all C(n, 2)
         pairings in one league arena, and add the results to results.json under the reference's keys
-        (elo.py:45-71).  Returns the new results per key."""
+        (elo.py:45-71).  Returns the new results per key.  openings: an opening book (a list of move lists, or
+        openings.parse_openings' forms "all:N" / a JSON file): each pairing's games 2k and 2k + 1 start from
+        opening k mod len(openings), once per colour; None = every game starts on the empty board.  The counts
+        keep their keys and meaning either way."""
         from .arena import game_of_env
         from .engine import LeagueEngine
+        from .openings import parse_openings
 
         names = list(names)
         for n in names:
@@ -289,9 +293,10 @@ class Elo:
         if len(set(names)) != len(names) or len(names) < 2:
             raise ValueError("compare_models needs at least two different models")
         pairings = list(itertools.combinations(range(len(names)), 2))
-        eng = LeagueEngine(game_of_env(self.model_database.env), self.players(names), pairings,
-                           games_per_pairing=num_games, seed=self.seed + 7919 * self.calls,
-                           search_threads=self.search_threads, dtype=self.dtype, device=self.device)
+        game = game_of_env(self.model_database.env)
+        eng = LeagueEngine(game, self.players(names), pairings, games_per_pairing=num_games,
+                           seed=self.seed + 7919 * self.calls, search_threads=self.search_threads, dtype=self.dtype,
+                           device=self.device, openings=parse_openings(openings, game))
         self.calls += 1
         try:
             breakdowns = eng.play()
@@ -338,15 +343,18 @@ def main(argv=None):
     parser.add_argument("--b", nargs="*", dest="board_size", help="board size: W H")
     parser.add_argument("--p", nargs="*", help="players (default: every registered model)")
     parser.add_argument("--games", type=int, default=100, help="games per pairing")
+    parser.add_argument("--openings", default=None,
+                        help="opening book: all:N (every N-ply opening) or a JSON file "
+                             "of move lists; each opening is played once per colour in every pairing")
     args = parser.parse_args(argv)
     env = {"connect4": Connect4Env, "tictactoe": TicTacToeEnv}[args.game](*[int(x) for x in args.board_size or []])
     elo = Elo(ModelDatabase(args.dir, env))
     if args.command == "calculate_elo":
         print(json.dumps(elo.calculate_elo(), indent=1, sort_keys=True))
     elif args.p:
-        print(json.dumps(elo.compare_models(*args.p, num_games=args.games), indent=1, sort_keys=True))
+        print(json.dumps(elo.compare_models(*args.p, num_games=args.games, openings=args.openings), indent=1, sort_keys=True))
     else:
-        print(json.dumps(elo.compare_all(num_games=args.games), indent=1, sort_keys=True))
+        print(json.dumps(elo.compare_all(num_games=args.games, openings=args.openings), indent=1, sort_keys=True))
 
 
 if __name__ == "__main__":

@@ -35,6 +35,7 @@ import torch
 from . import _lib, distributed
 from .arena import Arena
 from .evaluator import make_evaluator
+from .openings import validate_openings
 
 
 class EventTimer:
@@ -89,8 +90,12 @@ class SelfPlayEngine:
                  seed=0, subsequence0=None, rng="philox", max_games=None, device=None, dtype=torch.float16,
                  leaf_layout="nhwc", cpuct=4.0, x_noise=0.25, blocks_per_tree=0, bucket=256, opponent=None,
                  opponent_iterations=None, record=True, search_threads=1, leaf_dedup=None, opponent_alpha=None,
-                 opponent_strong_play=None, opponent_search_threads=None, eval_cache=None):
-        """opponent_alpha / opponent_strong_play / opponent_search_threads: the opposing MCTS side's own
+                 opponent_strong_play=None, opponent_search_threads=None, eval_cache=None, openings=None,
+                 opening_period=0):
+        """openings: an opening book, a list of move lists from the empty board (openings.py; include/spmcts.h
+        spmcts_games_set_openings): game id i starts from opening ((i mod opening_period) >> 1) mod len(openings),
+        its book plies played without a search; None = every game starts on the empty board.
+        opponent_alpha / opponent_strong_play / opponent_search_threads: the opposing MCTS side's own
         search settings (evaluation games: each side is built from its own container's kwargs,
         selfplayworker.py:71-81); None = the policy's.  dtype: the fused trunk's element type, fp16 by
         default (the reference's inference autocast, inference_worker.py:114-119) or bf16.  eval_cache: plies
@@ -165,6 +170,10 @@ class SelfPlayEngine:
             raise ValueError("eval_cache needs leaf dedup (pure evaluators, search_threads > 1)")
         if self.eval_cache:
             self.arena.set_eval_cache(self.eval_cache)
+        self.openings = None
+        if openings:
+            self.openings = validate_openings(game, openings)
+            self.arena.games_set_openings(self.openings, int(opening_period))
         self.n_games = n_games
         self.max_games = max_games
         # torch convolutions want few distinct shapes; the fused HIP tower takes any batch
@@ -506,6 +515,8 @@ class LanedEngine:
 
     def __init__(self, game, network, n_games=4096, lanes=2, seed=0, subsequence0=None, device=None, pack=True,
                  stagger=False, cross_dedup=None, lane_sizes=None, **kw):
+        # openings= / opening_period= (SelfPlayEngine): every lane gets the same book and assigns it by its
+        # lane-local game ids
         if lanes < 1 or n_games < lanes:
             raise ValueError(f"need 1 <= lanes <= n_games (lanes={lanes}, n_games={n_games})")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -827,7 +838,10 @@ class LeagueEngine:
 
     def __init__(self, game, players, pairings, games_per_pairing=100, seed=0, search_threads=4,
                  dtype=torch.float16, subsequence0=0, device=None, leaf_layout="nhwc", cpuct=4.0, x_noise=0.25,
-                 blocks_per_tree=0):
+                 blocks_per_tree=0, openings=None):
+        """openings: an opening book (openings.py) with id period g, the per-pairing slot count: every pairing
+        walks the suite from its first opening, slots 2k and 2k + 1 of a pairing play opening k mod len(openings)
+        once per colour.  None = every game starts on the empty board."""
         self.game = game
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.players = [dict(p) for p in players]
@@ -897,6 +911,12 @@ class LeagueEngine:
                 if hasattr(ev, "reserve"):
                     ev.reserve(max(1, a.league_seg[j + 1] - a.league_seg[j]), self.device)
         self.tree_net = tree_net
+        # all games start in the same ply, so the first min(len) plies are book plies of every game
+        self.openings, self.book_plies = None, 0
+        if openings:
+            self.openings = validate_openings(game, openings)
+            a.games_set_openings(self.openings, self.g)
+            self.book_plies = min(len(o) for o in self.openings)
         self.device_count = all(getattr(ev, "supports_device_count", False) for ev in self.evaluators)
         self.launches = 0  # network launches (one per network with rows to take, per step)
         self.plies = 0
@@ -920,6 +940,8 @@ class LeagueEngine:
         a = self.arena
         a.games_set_limit(self.n_slots)  # one game per slot, no refill
         a.games_start(list(range(self.n_slots)), priors=self._root_priors())
+        # the opening the device gave each slot's game (one game per slot: kept for results())
+        self.slot_opening = a.games_openings().tolist() if self.openings else None
         self.started = True
 
     def _eval_expand(self):
@@ -954,7 +976,8 @@ class LeagueEngine:
             self.start()
         a = self.arena
         a.games_begin_ply()
-        for step in range(self.select_steps):
+        # a ply every game plays from its book: no tree can be active, so no select and no network launch
+        for step in range(0 if self.plies < self.book_plies else self.select_steps):
             if step == 0 or self.search_threads == 1:
                 a.select_async()
             else:
@@ -980,13 +1003,25 @@ class LeagueEngine:
         return self.results()
 
     def results(self):
+        """Per pairing the totals {"first": ..., "second": ...}; with an opening book also "openings": {opening
+        index: the same two breakdowns over the games that started from it}."""
         r = self.arena.games_results()
         out = []
+
+        def empty():
+            return {"first": dict(wins=0, draws=0, losses=0), "second": dict(wins=0, draws=0, losses=0)}
+
         for first, _, _ in self.schedule:
-            b = {"first": dict(wins=0, draws=0, losses=0), "second": dict(wins=0, draws=0, losses=0)}
+            b = empty()
+            per = {}
             for s in range(first, first + self.g):
-                side = b["second" if r["swap"][s] else "first"]
-                side["wins" if r["result"][s] == 1 else ("draws" if r["result"][s] == 0 else "losses")] += 1
+                key = "wins" if r["result"][s] == 1 else ("draws" if r["result"][s] == 0 else "losses")
+                b["second" if r["swap"][s] else "first"][key] += 1
+                if self.openings:
+                    o = self.slot_opening[s]  # ((s - first) >> 1) % len(openings): the game's id mod g is s - first
+                    per.setdefault(o, empty())["second" if r["swap"][s] else "first"][key] += 1
+            if self.openings:
+                b["openings"] = per
             out.append(b)
         return out
 

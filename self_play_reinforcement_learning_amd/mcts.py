@@ -184,6 +184,18 @@ class MCTreeSearch(Policy):
         """Advance the root; an unvisited child is expanded and backed up (mcts.py:188-209)."""
         self._eval_expand(self._arena.play_action([0], [int(action)]))
 
+    def set_position(self, moves, player=1):
+        """The tree of a position given as a move sequence from the empty board: reset(player), then
+        play_action(m) for each move (the state the reference's MCTreeSearch is in after the same calls).  The
+        single-tree form of analyse_positions' chain; the moves are validated first (openings.py)."""
+        from .openings import validate_openings
+
+        seq = validate_openings(self.game, [moves])[0]
+        self.reset(player)
+        for a in seq:
+            self.play_action(a)
+        return self.root_node.state
+
     @property
     def root_node(self):
         return RootView(self._arena.root_stats(0))
@@ -250,3 +262,54 @@ class MCTreeSearch(Policy):
     def evaluate(self, evaluate_state=False):
         """Evaluate mode plays with temp / 20 (mcts.py:273-274, :392-394)."""
         self.evaluating = evaluate_state
+
+
+@torch.no_grad()
+def analyse_positions(game, network, positions, iterations, search_threads=1, x_noise=0.25, seed=0, alpha=1.0,
+                      strong_play=False, cpuct=4.0, player=1, device=None, dtype=torch.float16, rng="philox"):
+    """The search's answer for a batch of positions, each a move sequence from the empty board.
+
+    One tree-mode arena of one tree per position: reset(player), one play_action step per ply (a tree whose
+    sequence is shorter sits out), one search of `iterations` simulations (search_threads in flight per tree),
+    then one Arena.root_stats_batch call.  Each tree is in the state MCTreeSearch.set_position(moves) followed by
+    search() leaves it in; tree t draws from Philox subsequence t of `seed`.  Returns device tensors: child_n int32
+    [n, A] (visit counts), child_w float64 [n, A], child_p float32 [n, A] (priors), root_n, root_w, root_q float64
+    [n] (w / n of the root, 0 where n is 0), root_player int8 [n], action int64 [n] (the most visited child, the
+    lowest index on ties), board int8 [n, W, H] (tree frame)."""
+    from .openings import validate_openings
+
+    game = game if isinstance(game, str) else game_of_env(game)
+    seqs = validate_openings(game, positions)
+    n = len(seqs)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if isinstance(network, torch.nn.Module):
+        network = network.to(dev)
+    ev = make_evaluator(network, game, device=dev, dtype=dtype)
+    arena = Arena(game, n_trees=max(n, 1), n_games=0, iterations=iterations, rng=rng, seed=seed,
+                  strong_play=strong_play, leaf_format=ev.leaf_format, leaf_layout=ev.leaf_layout, cpuct=cpuct,
+                  x_noise=x_noise, alpha=alpha, device=dev, search_threads=search_threads)
+    try:
+        def eval_expand(count):
+            if count:
+                probs, values = ev(arena.leaves(count))
+                arena.expand(probs, values)
+
+        probs, _ = ev(ev.empty_root_input(arena.W, arena.H, dev))
+        arena.set_root_prior(probs[0])
+        trees = list(range(n))
+        if n:
+            arena.tree_reset(trees, [player] * n)
+            for i in range(max(len(s) for s in seqs)):
+                on = [t for t in trees if i < len(seqs[t])]
+                eval_expand(arena.play_action(on, [seqs[t][i] for t in on]))
+            arena.search_begin(trees)
+            for _ in range(-(-iterations // arena.search_threads)):
+                eval_expand(arena.select())
+        out = arena.root_stats_batch(trees)
+        rn = out["root_n"].to(torch.float64)
+        out["root_q"] = torch.where(rn > 0, out["root_w"] / rn.clamp(min=1), torch.zeros_like(rn))
+        out["action"] = out["child_n"].argmax(dim=1) if n else torch.zeros(0, dtype=torch.int64, device=dev)
+        arena.check()
+    finally:
+        arena.close()
+    return out

@@ -419,7 +419,7 @@ class SelfPlayScheduler:
                          opponent_strong_play=kw.get("strong_play", False),
                          opponent_search_threads=self._opponent_threads)
 
-    def _evaluation_engine(self, n_games):
+    def _evaluation_engine(self, n_games, openings=None):
         opponent, opp_kw = self._opponent()
         kw = self._policy_kwargs()
         per_rank = max(1, n_games // self.world + (1 if self.rank < n_games % self.world else 0))
@@ -428,14 +428,15 @@ class SelfPlayScheduler:
         return SelfPlayEngine(self.game, self.network, n_games=slots, iterations=kw.get("iterations", 100),
                               alpha=kw.get("alpha", 1), strong_play=kw.get("strong_play", False), evaluate=True,
                               seed=self.seed + 104729 + 7919 * self.rank, device=self.device, opponent=opponent,
-                              record=False, search_threads=self._search_threads, **opp_kw), per_rank
+                              record=False, search_threads=self._search_threads, openings=openings, **opp_kw), per_rank
 
-    def _play_evaluation(self, n_games):
+    def _play_evaluation(self, n_games, openings=None):
         """n_games evaluation games over all ranks (task i -> swap_sides = i odd, update=False);
-        returns the reference's result dicts (self_play_parallel.py:294-300, :366-371)."""
+        returns the reference's result dicts (self_play_parallel.py:294-300, :366-371).  openings: an opening
+        book (each rank's game i starts from opening (i >> 1) mod len(openings))."""
         if n_games <= 0:
             return []
-        eng, per_rank = self._evaluation_engine(n_games)
+        eng, per_rank = self._evaluation_engine(n_games, openings)
         c0 = eng.counters()["results"]
         eng.play_games(per_rank)
         eng.check()
@@ -494,20 +495,25 @@ class SelfPlayScheduler:
         return total
 
     def compare_models(self, num_workers=None, inference_proxy=True, threads_per_worker=8, resume_model=False,
-                       gpus=None):
+                       gpus=None, openings=None):
         """self_play_parallel.py:355-379: epoch_length evaluation games, policy network vs the
         evaluation policy (a second network on the same arena, or a hard-coded player).
         Returns (total_rewards, breakdown) exactly as the reference's parse_results; with gpus > 1
-        the games are sharded over one rank process per GPU."""
+        the games are sharded over one rank process per GPU.  openings: an opening book (openings.py: a list of
+        move lists, "all:N", or a JSON file); games 2k and 2k + 1 start from opening k mod len(openings), once
+        per colour; None = every game starts on the empty board."""
+        from .openings import parse_openings
+
+        openings = parse_openings(openings, self.game)
         n = self._ranks(gpus)
         if n > 1:
             return self._run_ranks(n, "compare_models", dict(num_workers=num_workers, inference_proxy=inference_proxy,
                                                               threads_per_worker=threads_per_worker,
-                                                              resume_model=resume_model))
+                                                              resume_model=resume_model, openings=openings))
         if resume_model:
             self._load_latest(prev_run=True)
         self._resolve_threads(inference_proxy)  # evaluation workers talk to the InferenceProxy too
-        reward_list = self._play_evaluation(self.epoch_length)
+        reward_list = self._play_evaluation(self.epoch_length, openings)
         return self.parse_results(reward_list)
 
 
