@@ -58,7 +58,9 @@ enum spmcts_layout { SPMCTS_NCHW = 0, SPMCTS_NHWC = 1 };
 enum spmcts_player_kind {
   SPMCTS_PLAYER_MCTS = 0,     /* MCTreeSearch (the default)                                 */
   SPMCTS_PLAYER_RANDOM = 1,   /* Random: uniform over valid moves (hardcoded_players.py:36-56) */
-  SPMCTS_PLAYER_LOOKAHEAD = 2 /* OneStepLookahead: win / block / random (:8-33)               */
+  SPMCTS_PLAYER_LOOKAHEAD = 2,/* OneStepLookahead: win / block / random (:8-33)               */
+  SPMCTS_PLAYER_NEGAMAX = 3   /* exact depth-limited negamax (no reference form): uniform over the moves with
+                                 the best code of spmcts_negamax_batch at the tree's depth        */
 };
 
 /* return code of the tower entry points (spmcts_tower_forward*, spmcts_tower_heads*): an environment switch
@@ -174,7 +176,11 @@ int spmcts_expand2(spmcts_arena *h, const float *probs0_dev, const float *values
  * compare_models, self_play_parallel.py:355-379).  Host arrays of n_trees entries, each
  * may be NULL (default): nets = network id 0/1 of the tree's leaves; kinds = enum
  * spmcts_player_kind; budgets = simulations per search (MCTreeSearch.iterations of that
- * player; < 0 = unlimited).  Network-1 leaves are placed from row seg1 = #network-0 trees. */
+ * player; < 0 = unlimited).  Network-1 leaves are placed from row seg1 = #network-0 trees.
+ * For a tree of kind SPMCTS_PLAYER_NEGAMAX budgets[t] is its depth, 1 .. 6; anything else (budgets NULL
+ * included) returns -3.  The first call that names such a tree allocates the arena's int8 [n_trees][A] score
+ * rows; from then on spmcts_games_end_ply solves the positions of the games whose mover is such a tree before
+ * it plays the ply.  An arena without such a tree launches and allocates nothing more than before. */
 int spmcts_set_tree_players(spmcts_arena *h, const uint8_t *nets, const uint8_t *kinds, const int32_t *budgets);
 /* (sync) Per-tree search settings: each side of an evaluation game searches with its own
  * MCTreeSearch kwargs (selfplayworker.py:71-81 builds the opponent from its own container;
@@ -368,6 +374,31 @@ int spmcts_env_step(int32_t game, int32_t width, int32_t height, const int8_t *b
 int spmcts_env_step_host(int32_t game, int32_t width, int32_t height, int8_t *board /*[W][H] in/out*/,
                          int32_t action, int32_t player, int32_t *reward, int32_t *done);
 int spmcts_valid_moves_host(int32_t game, int32_t width, int32_t height, const int8_t *board, uint8_t *valid);
+/* ---- exact depth-limited negamax (csrc/negamax.h) -------------------------------------------------------------
+ * A position is seen from the side to move.  For a depth D >= 1 every action gets one int8 code:
+ *   +k (k odd, 1 <= k <= D)   playing it, the mover forces a win within k plies and not sooner (the move is ply 1)
+ *   -k (k even, 2 <= k <= D)  every line loses by force; k = the latest ply the loss can be delayed to
+ *    0                        not decided within D plies (a full-board draw and the horizon are both 0)
+ *   -128                      an illegal move
+ * Preference: +1 > +3 > ... > 0 > ... > -4 > -2.  Legal moves, wins and full boards are those of
+ * spmcts_env_step_host.  The position is assumed not to be finished: a board that already holds a line is
+ * searched as if play went on.  The search is full width; nodes = moves made (it stops at wins, full boards
+ * and the horizon). */
+/* The deepest D: 9 for TicTacToe (a full solve), 8 for the Connect4 boards; -2 for a board not instantiated. */
+int spmcts_negamax_max_depth(int32_t game, int32_t width, int32_t height);
+/* Positions per kernel launch at this depth: spmcts_negamax_batch splits a larger batch, so that no launch's
+ * worst-case node bound, positions * sum_{k <= D} A^k, exceeds a constant (csrc/spmcts.hip NM_LAUNCH_NODES). */
+int spmcts_negamax_launch_positions(int32_t game, int32_t width, int32_t height, int32_t depth);
+/* Host twin (the kernel's search core compiled for the host; no GPU): board int8 [W][H] of +-1 stones, player =
+ * the side to move; scores int8 [A], nodes (may be NULL).  -3 for a depth outside [1, max_depth]. */
+int spmcts_negamax_host(int32_t game, int32_t width, int32_t height, const int8_t *board /*[W][H]*/, int32_t player,
+                        int32_t depth, int8_t *scores /*[A]*/, uint64_t *nodes);
+/* n positions on the device: boards_dev int8 [n][W][H], players_dev int8 [n] -> scores_dev int8 [n][A],
+ * nodes_dev uint64 [n] (may be NULL).  No arena, asynchronous on `stream`; n = 0 is a no-op; -3 (with a
+ * spmcts_last_error text) for a depth outside [1, max_depth].  Bit-equal to the host twin. */
+int spmcts_negamax_batch(int32_t game, int32_t width, int32_t height, const int8_t *boards_dev,
+                         const int8_t *players_dev, int32_t n, int32_t depth, int8_t *scores_dev, uint64_t *nodes_dev,
+                         spmcts_stream stream);
 /* Deterministic table network (oracle/table_net.py) over leaf rows, for bit-exact
  * search parity tests: leaves in any spmcts_leaf_format/layout; per-row salts optional. */
 int spmcts_table_net(int32_t game, int32_t width, int32_t height, const void *leaves_dev, int32_t leaf_format,

@@ -9,9 +9,11 @@ Public API mirrors the reference:
     ResidualTower                         (games/general/modules.py)
     Connect4Env, TicTacToeEnv             (games/connect4, games/tictactoe)
     OneStepLookahead, Random              (games/general/hardcoded_players.py)
+    Negamax                               (no reference form: looks `depth` plies ahead, exactly)
     Elo, ModelDatabase                    (games/algos/elo.py, games/algos/model_database.py)
 plus the arena itself: Arena, SelfPlayEngine, LanedEngine, LeagueEngine, DeviceTableNet, and what the reference
-has no form of: opening books (openings.py: enumerate_openings, validate_openings) and analyse_positions.
+has no form of: opening books (openings.py: enumerate_openings, validate_openings), analyse_positions, and the
+exact depth-limited solver (solve_positions, tactical_report).
 """
 from .base_model import BasePlayer, ModelContainer, Policy, TrainableModel  # noqa: F401
 from .memory import Memory  # noqa: F401
@@ -29,6 +31,8 @@ _LAZY = {
     "MCTreeSearch": ".mcts",
     "Move": ".mcts",
     "analyse_positions": ".mcts",
+    "solve_positions": ".mcts",
+    "tactical_report": ".mcts",
     "enumerate_openings": ".openings",
     "validate_openings": ".openings",
     "SelfPlayScheduler": ".self_play_parallel",
@@ -37,6 +41,7 @@ _LAZY = {
     "GameOver": ".envs",
     "OneStepLookahead": ".hardcoded_players",
     "Random": ".hardcoded_players",
+    "Negamax": ".hardcoded_players",
 }
 
 

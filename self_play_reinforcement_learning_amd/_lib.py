@@ -19,7 +19,7 @@ TOWER_F16 = 2  # fp16 weights / activations / head features (include/spmcts.h SP
 LEAF_F32, LEAF_F16, LEAF_BF16, LEAF_BOARD_I64 = 0, 1, 2, 3
 WLAYOUT_32X32, WLAYOUT_M16 = 0, 1  # spmcts_tower_weight_layout (include/spmcts.h SPMCTS_WLAYOUT_*)
 NCHW, NHWC = 0, 1
-PLAYER_MCTS, PLAYER_RANDOM, PLAYER_LOOKAHEAD = 0, 1, 2
+PLAYER_MCTS, PLAYER_RANDOM, PLAYER_LOOKAHEAD, PLAYER_NEGAMAX = 0, 1, 2, 3
 
 ERR_FLAGS = {
     0x1: "node pool exhausted",
@@ -132,6 +132,10 @@ _SIGS = {
     "spmcts_env_step": [_I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P],
     "spmcts_env_step_host": [_I32, _I32, _I32, _P, _I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)],
     "spmcts_valid_moves_host": [_I32, _I32, _I32, _P, _P],
+    "spmcts_negamax_max_depth": [_I32, _I32, _I32],
+    "spmcts_negamax_launch_positions": [_I32, _I32, _I32, _I32],
+    "spmcts_negamax_host": [_I32, _I32, _I32, _P, _I32, _I32, _P, ctypes.POINTER(_U64)],
+    "spmcts_negamax_batch": [_I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P],
     "spmcts_table_net": [_I32, _I32, _I32, _P, _I32, _I32, _I32, _U64, _P, _P, _P, _P],
     "spmcts_set_leaf_dedup": [_P, _I32],
     "spmcts_set_leaf_peer": [_P, _P],

@@ -26,10 +26,6 @@ __device__ void start_game(const View &v, int g, int64_t id, const float *priors
   }
 }
 
-// The game plays a move of its opening this ply (SelfPlayer.play_move, selfplayworker.py:221-224, on a given
-// action): no search, no noise, no random number, no Move record.
-__device__ __forceinline__ bool in_book(const View &v, int g) { return v.book_n && v.gply[g] < v.gbook[g]; }
-
 template <class G>
 __global__ void k_games_start(View v, const int32_t *slots, const float *priors, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -74,7 +70,8 @@ __global__ void k_games_begin_ply(View v) {
 // OneStepLookahead (:18-33): first any move after which step(a, look) ends the game, then any move
 // after which step(a, -look) does, else uniform over the legal moves.  Random (:45-49): uniform.
 // The uniform draw uses the tree's Philox stream (the reference's `random` module stream is not
-// reproduced).
+// reproduced).  Negamax (no reference form; negamax.h): uniform over the moves with the best code, the
+// int(u * n)-th of them in ascending action order, one draw like the uniform fallback's.
 template <class G>
 __device__ int hardcoded_move(const View &v, int tree, int kind, Board envb, int look) {
   const uint32_t legal = legal_mask<G>(envb);
@@ -90,7 +87,24 @@ __device__ int hardcoded_move(const View &v, int tree, int kind, Board envb, int
       }
     }
   }
-  const int n = popc((uint64_t)legal);
+  // the moves the draw chooses among: the legal ones, or for Negamax (negamax.h; k_negamax_games wrote the
+  // tree's codes before this kernel) the legal ones whose code is best in the order +1 > +3 > ... > 0 > ... > -2
+  uint32_t cand = legal;
+  if (kind == SPMCTS_PLAYER_NEGAMAX) {
+    const int8_t *code = v.nm_score + (size_t)tree * G::A;
+    int best = -1024;
+    cand = 0;
+    for (int a = 0; a < G::A; ++a) {
+      if (!((legal >> a) & 1u)) continue;
+      const int rk = nm_rank(code[a]);
+      if (rk > best) {
+        best = rk;
+        cand = 0;
+      }
+      if (rk == best) cand |= 1u << a;
+    }
+  }
+  const int n = popc((uint64_t)cand);
   if (n == 0) return 0;
   TreeRng r;
   rng_load(v, tree, r);
@@ -101,7 +115,7 @@ __device__ int hardcoded_move(const View &v, int tree, int kind, Board envb, int
   int k = (int)(u * (double)n);
   if (k >= n) k = n - 1;
   for (int a = 0; a < G::A; ++a)
-    if ((legal >> a) & 1u) {
+    if ((cand >> a) & 1u) {
       if (k == 0) return a;
       --k;
     }

@@ -125,6 +125,9 @@ struct View {
   int32_t *book_lens;   // [BOOK_MAX_OPENINGS]
   int32_t *gopen;       // [G] the game's opening (-1: none)
   int32_t *gbook;       // [G] that opening's length (0: none)
+  // negamax players (SPMCTS_PLAYER_NEGAMAX, negamax.h): the codes of each tree's moves for the ply, int8 [T][A],
+  // written by k_negamax_games before k_games_end_ply reads them; null until a tree of the kind is set
+  int8_t *nm_score;
 };
 
 enum { BOOK_MAX_OPENINGS = 65536 };
@@ -200,3 +203,6 @@ __device__ __forceinline__ int dom_slot(const View &v, int c) {
   return tree < 0 ? -1 : tree * v.K + (c - i * v.K);
 }
 
+// The game plays a move of its opening this ply (SelfPlayer.play_move, selfplayworker.py:221-224, on a given
+// action): no search, no noise, no random number, no Move record.
+__device__ __forceinline__ bool in_book(const View &v, int g) { return v.book_n && v.gply[g] < v.gbook[g]; }

@@ -31,7 +31,8 @@
 //   arena_select.h  resets and noise, k_compact, DPP reductions, k_select, the threaded sim and slot fill
 //   arena_rows.h    leaf dedup, evaluation cache, peer push, k_scan_need, k_encode
 //   arena_expand.h  k_expand, threaded expand and select (one slot-cycle walk), _play, k_search_end, set_node, k_play_action
-//   arena_games.h   game state machine (opening book plies included), k_root_stats_batch, export
+//   negamax.h       exact depth-limited negamax: the search core (host and device), its batch and arena kernels
+//   arena_games.h   game state machine (opening book plies included), the hard-coded players, k_root_stats_batch, export
 //   arena_misc.h    k_env_step, k_table_net, k_copy_probe, the init kernels
 //   arena_league.h  league routing: a step's rows partitioned by their tree's network, and back
 //
@@ -87,6 +88,7 @@ static int fail(int code, const std::string &msg) {
 #include "arena_select.h"
 #include "arena_rows.h"
 #include "arena_expand.h"
+#include "negamax.h"
 #include "arena_games.h"
 #include "arena_misc.h"
 #include "arena_league.h"
@@ -127,6 +129,11 @@ struct spmcts_arena {
   std::vector<int32_t> lg_seg;
   std::vector<void *> league_allocs;
   bool route_step = false;
+  // negamax players (spmcts_set_tree_players): the score rows' allocation (View::nm_score), whether any tree is
+  // of the kind, and the deepest horizon among them (sizes the launches of spmcts_games_end_ply)
+  void *nm_alloc = nullptr;
+  bool nm_on = false;
+  int nm_depth = 0;
 };
 
 static bool league_on(const spmcts_arena *h) { return h->lg.n > 0; }
@@ -354,6 +361,44 @@ static int launch(void (*k)(P...), long long n, int B, hipStream_t s, const A &.
 #define LAUNCH(h, k, n, B, s, ...) \
   with_game((h)->cfg.game, (h)->W, (h)->H, [&](auto game_) { return launch(k<decltype(game_)>, n, B, s, __VA_ARGS__); })
 
+// ---- negamax launches --------------------------------------------------------
+// A launch's worst-case node bound, positions * sum_{k = 1 .. D} A^k, stays below NM_LAUNCH_NODES: a batch (and
+// an arena's games) is split into launches of nm_launch_positions positions.  Measured on one MI355X (DESIGN.md
+// §4 "Exact depth-limited negamax", profiles/negamax/): 8.9e10 nodes/s at depth 6 (4,096 positions in one
+// launch), 2.7e10 nodes/s at depth 8 with launches of 594 positions (4.0e9: 455 waves, under half of the chip's
+// 1,024 SIMDs).  At the lower of the two rates a launch of 8.0e9 nodes, the bound's worst case, takes 0.3 s;
+// the launches of a depth-8 batch then hold 1,188 positions (910 waves), and the same batch measured 4.8e10
+// nodes/s: 0.13 s per launch, 0.17 s for one at the bound.
+static const double NM_LAUNCH_NODES = 8.0e9;
+
+static long long nm_launch_positions(int A, int depth) {
+  double bound = 0, term = 1;
+  for (int k = 1; k <= depth; ++k) {
+    term *= A;
+    bound += term;
+  }
+  const double n = NM_LAUNCH_NODES / bound;
+  return n < 1 ? 1 : (n > (double)(1 << 24) ? (1 << 24) : (long long)n);
+}
+
+// k over positions [0, n) in launches of at most `per` positions: f(first position, count) launches one
+template <class G, class F>
+static int nm_launches(long long n, int depth, F &&f) {
+  const long long per = nm_launch_positions(G::A, depth);
+  for (long long p0 = 0; p0 < n; p0 += per) TRY(f(p0, (int)std::min(per, n - p0)));
+  return 0;
+}
+
+static int negamax_games(spmcts_arena *h, hipStream_t s) {
+  return with_game(h->cfg.game, h->W, h->H, [&](auto g) {
+    using G = decltype(g);
+    return nm_launches<G>(h->v.G, h->nm_depth, [&](long long g0, int n) {
+      return launch(k_negamax_games<G>, ((long long)n + NmGrid<G>::PPB - 1) / NmGrid<G>::PPB * NM_THREADS, NM_THREADS, s,
+                    h->v, (int)g0, n);
+    });
+  });
+}
+
 extern "C" {
 
 int spmcts_version(void) { return 1; }
@@ -429,6 +474,7 @@ int spmcts_arena_destroy(spmcts_arena *h) {
   for (void *p : h->allocs) (void)hipFree(p);
   for (void *p : h->cache_allocs) (void)hipFree(p);
   for (void *p : h->league_allocs) (void)hipFree(p);
+  if (h->nm_alloc) (void)hipFree(h->nm_alloc);
   delete h;
   return 0;
 }
@@ -669,18 +715,32 @@ int spmcts_set_tree_players(spmcts_arena *h, const uint8_t *nets, const uint8_t 
   const int T = h->v.T;
   std::vector<uint8_t> nt(T, 0), kd(T, SPMCTS_PLAYER_MCTS);
   std::vector<int32_t> bd(T, 0x7fffffff);
-  int n0 = 0;
+  int n0 = 0, nm_depth = 0;
+  const int nm_cap = with_game(h->cfg.game, h->W, h->H, [](auto g) { return (int)NmCap<decltype(g)>::PLAYER; });
   for (int t = 0; t < T; ++t) {
     if (nets) nt[t] = nets[t] ? 1 : 0;
     if (kinds) {
-      if (kinds[t] > SPMCTS_PLAYER_LOOKAHEAD) return fail(-3, "unknown player kind");
+      if (kinds[t] > SPMCTS_PLAYER_NEGAMAX) return fail(-3, "unknown player kind");
       kd[t] = kinds[t];
     }
     if (budgets) bd[t] = budgets[t] < 0 ? 0x7fffffff : budgets[t];
+    if (kd[t] == SPMCTS_PLAYER_NEGAMAX) {  // its budget is its horizon
+      if (!budgets || budgets[t] < 1 || budgets[t] > nm_cap)
+        return fail(-3, "a negamax player's budget is its depth: 1 .. " + std::to_string(nm_cap));
+      nm_depth = std::max(nm_depth, budgets[t]);
+    }
     n0 += nt[t] ? 0 : 1;
   }
   if (league_on(h) && n0 < T) return fail(-3, LEAGUE_EXCLUDES);
   HIP_TRY(hipDeviceSynchronize());
+  if (nm_depth && !h->nm_alloc) {  // the first tree of the kind: its arena gets the score rows
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMalloc(&h->nm_alloc, (size_t)T * h->A));
+    HIP_TRY(hipMemset(h->nm_alloc, 0, (size_t)T * h->A));
+    h->v.nm_score = (int8_t *)h->nm_alloc;
+  }
+  h->nm_on = nm_depth > 0;
+  h->nm_depth = nm_depth;
   HIP_TRY(hipMemcpy(h->v.tnet, nt.data(), T, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->v.tkind, kd.data(), T, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->v.budget, bd.data(), 4 * (size_t)T, hipMemcpyHostToDevice));
@@ -910,6 +970,7 @@ int spmcts_games_begin_ply(spmcts_arena *h, spmcts_stream stream) {
 int spmcts_games_end_ply(spmcts_arena *h, void *leaves_dev, int32_t *leaf_count_dev, spmcts_stream stream) {
   if (!h) return fail(-1, "null arena");
   hipStream_t s = (hipStream_t)stream;
+  if (h->nm_on) TRY(negamax_games(h, s));  // the negamax movers' codes, read by k_games_end_ply
   TRY(LAUNCH(h, k_games_end_ply, h->v.G, 64, s, h->v));
   return launch_rows(h, leaves_dev, leaf_count_dev, s, false);
 }
@@ -1213,6 +1274,49 @@ int spmcts_valid_moves_host(int32_t game, int32_t width, int32_t height, const i
     const uint32_t m = legal_mask<G>(from_cells<G>(board));
     for (int a = 0; a < G::A; ++a) valid[a] = (m >> a) & 1u;
     return 0;
+  });
+}
+
+// ---- negamax -------------------------------------------------------------------
+int spmcts_negamax_max_depth(int32_t game, int32_t width, int32_t height) {
+  return with_game(game, width, height, [](auto g) { return (int)NmCap<decltype(g)>::DEPTH; });
+}
+
+int spmcts_negamax_launch_positions(int32_t game, int32_t width, int32_t height, int32_t depth) {
+  const int cap = spmcts_negamax_max_depth(game, width, height);
+  if (cap < 0) return cap;
+  if (depth < 1 || depth > cap) return fail(-3, "negamax depth: 1 .. " + std::to_string(cap));
+  return with_game(game, width, height,
+                   [&](auto g) { return (int)std::min<long long>(nm_launch_positions(decltype(g)::A, depth), 0x7fffffff); });
+}
+
+int spmcts_negamax_host(int32_t game, int32_t width, int32_t height, const int8_t *board, int32_t player, int32_t depth,
+                        int8_t *scores, uint64_t *nodes) {
+  const int cap = spmcts_negamax_max_depth(game, width, height);
+  if (cap < 0) return cap;
+  if (!board || !scores) return fail(-1, "null argument");
+  if (depth < 1 || depth > cap) return fail(-3, "negamax depth: 1 .. " + std::to_string(cap));
+  return with_game(game, width, height, [&](auto g) {
+    using G = decltype(g);
+    const Board b = from_cells<G>(board);
+    nm_solve_host<G>(player > 0 ? b.pos : b.neg, player > 0 ? b.neg : b.pos, depth, scores, nodes);
+    return 0;
+  });
+}
+
+int spmcts_negamax_batch(int32_t game, int32_t width, int32_t height, const int8_t *boards_dev, const int8_t *players_dev,
+                         int32_t n, int32_t depth, int8_t *scores_dev, uint64_t *nodes_dev, spmcts_stream stream) {
+  const int cap = spmcts_negamax_max_depth(game, width, height);
+  if (cap < 0) return cap;
+  if (depth < 1 || depth > cap) return fail(-3, "negamax depth: 1 .. " + std::to_string(cap));
+  if (n <= 0) return 0;
+  if (!boards_dev || !players_dev || !scores_dev) return fail(-1, "null argument");
+  return with_game(game, width, height, [&](auto g) {
+    using G = decltype(g);
+    return nm_launches<G>(n, depth, [&](long long p0, int m) {
+      return launch(k_negamax_batch<G>, ((long long)m + NmGrid<G>::PPB - 1) / NmGrid<G>::PPB * NM_THREADS, NM_THREADS,
+                    (hipStream_t)stream, boards_dev, players_dev, p0, m, depth, scores_dev, nodes_dev);
+    });
   });
 }
 

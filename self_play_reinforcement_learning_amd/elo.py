@@ -2,6 +2,7 @@
 
     db = ModelDatabase("ratings/connect4", Connect4Env)
     db.add_model("random", ModelContainer(Random))
+    db.add_model("nm4", ModelContainer(Negamax, policy_kwargs=dict(depth=4)))   # a fixed rung: 4 plies, exactly
     db.add_model("net1", ModelContainer(MCTreeSearch, policy_kwargs=dict(network=net, iterations=200)))
     elo = Elo(db)
     elo.compare_models("random", "net1")      # every pairing in ONE league arena (engine.LeagueEngine)
@@ -35,7 +36,7 @@ import torch
 
 from .base_model import ModelContainer
 
-POLICIES = ("MCTreeSearch", "Random", "OneStepLookahead")
+POLICIES = ("MCTreeSearch", "Random", "OneStepLookahead", "Negamax")
 _JSON_SCALARS = (bool, int, float, str, type(None))
 
 
@@ -271,6 +272,8 @@ class Elo:
                 out.append(dict(network=self.model_database.network(name), iterations=int(kw.get("iterations", 100)),
                                 alpha=float(kw.get("alpha", 1)), strong_play=bool(kw.get("strong_play", False)),
                                 search_threads=self.search_threads))
+            elif e["policy"] == "Negamax":
+                out.append(dict(kind="negamax", depth=int(e["policy_kwargs"].get("depth", 2))))
             else:
                 out.append(dict(kind="random" if e["policy"] == "Random" else "lookahead"))
         return out

@@ -23,7 +23,8 @@ Evaluation games (SelfPlayWorker.set_up_policies(evaluate=True),
 selfplayworker.py:68-94; compare_models, self_play_parallel.py:355-379): pass
 `opponent=` a second network (its trees' leaves go to a second row segment
 evaluated by that network), or "random" / "lookahead" for the hard-coded
-players of games/general/hardcoded_players.py, optionally with its own
+players of games/general/hardcoded_players.py, or "negamax" (with
+`opponent_depth`: the exact depth-limited player), optionally with its own
 `opponent_iterations`; `record=False` skips Move records (update=False).
 """
 import contextlib
@@ -70,6 +71,16 @@ class EventTimer:
         return [(ref.elapsed_time(a), ref.elapsed_time(b)) for a, b in self.pairs if b is not None]
 
 
+NEGAMAX_PLAYER_DEPTH = 6  # the arena player's deepest horizon (csrc/negamax.h NmCap::PLAYER)
+
+
+def negamax_depth(depth):
+    """The depth of a device negamax player as an int; ValueError outside [1, NEGAMAX_PLAYER_DEPTH]."""
+    if isinstance(depth, bool) or not isinstance(depth, int) or not 1 <= depth <= NEGAMAX_PLAYER_DEPTH:
+        raise ValueError(f"a negamax player's depth must be an integer in [1, {NEGAMAX_PLAYER_DEPTH}], got {depth!r}")
+    return depth
+
+
 def union_ms(intervals):
     """Length of the union of [start, end) intervals (ms): busy time of possibly overlapping launches."""
     total, cur_s, cur_e = 0.0, None, None
@@ -91,8 +102,9 @@ class SelfPlayEngine:
                  leaf_layout="nhwc", cpuct=4.0, x_noise=0.25, blocks_per_tree=0, bucket=256, opponent=None,
                  opponent_iterations=None, record=True, search_threads=1, leaf_dedup=None, opponent_alpha=None,
                  opponent_strong_play=None, opponent_search_threads=None, eval_cache=None, openings=None,
-                 opening_period=0):
-        """openings: an opening book, a list of move lists from the empty board (openings.py; include/spmcts.h
+                 opening_period=0, opponent_depth=2):
+        """opponent_depth: the horizon of opponent="negamax" (hardcoded_players.Negamax; 1 .. 6 on the device).
+        openings: an opening book, a list of move lists from the empty board (openings.py; include/spmcts.h
         spmcts_games_set_openings): game id i starts from opening ((i mod opening_period) >> 1) mod len(openings),
         its book plies played without a search; None = every game starts on the empty board.
         opponent_alpha / opponent_strong_play / opponent_search_threads: the opposing MCTS side's own
@@ -110,9 +122,9 @@ class SelfPlayEngine:
         opp_kind = _lib.PLAYER_MCTS
         if isinstance(opponent, str):
             kinds = {"random": _lib.PLAYER_RANDOM, "lookahead": _lib.PLAYER_LOOKAHEAD,
-                     "onesteplookahead": _lib.PLAYER_LOOKAHEAD}
+                     "onesteplookahead": _lib.PLAYER_LOOKAHEAD, "negamax": _lib.PLAYER_NEGAMAX}
             if opponent.lower() not in kinds:
-                raise ValueError(f"unknown hard-coded opponent {opponent!r} (random / lookahead)")
+                raise ValueError(f"unknown hard-coded opponent {opponent!r} (random / lookahead / negamax)")
             opp_kind = kinds[opponent.lower()]
         elif opponent is not None and opponent is not network:
             self.evaluator1 = make_evaluator(opponent, game, device=self.device, dtype=dtype, leaf_layout=leaf_layout)
@@ -148,7 +160,8 @@ class SelfPlayEngine:
             # tree 2g = the policy, 2g + 1 = the opposing player (selfplayworker.py:164-176)
             self.arena.set_tree_players(nets=[0, 1 if self.evaluator1 is not None else 0] * n_games,
                                         kinds=[_lib.PLAYER_MCTS, opp_kind] * n_games,
-                                        budgets=[iterations, it1] * n_games)
+                                        budgets=[iterations, negamax_depth(opponent_depth)
+                                                 if opp_kind == _lib.PLAYER_NEGAMAX else it1] * n_games)
         if not record:
             self.arena.games_set_record(False)
         # batch leaf dedup (include/spmcts.h spmcts_set_leaf_dedup): one row per distinct position of a
@@ -825,7 +838,7 @@ class LeagueEngine:
 
     players: a list of dicts, each either {"network": ResidualTower (or anything make_evaluator takes),
     "iterations", "alpha", "strong_play", "search_threads"} (the MCTreeSearch kwargs of that model's container)
-    or {"kind": "random" | "lookahead"} (hardcoded_players.py).  pairings: [(i, j), ...] indices into players.
+    or {"kind": "random" | "lookahead"} or {"kind": "negamax", "depth": d} (hardcoded_players.py).  pairings: [(i, j), ...] indices into players.
     Slot s of pairing (i, j) plays one game: tree 2s is player i, tree 2s + 1 player j, both in evaluate mode,
     no Move records, no refill.  Each simulation step's leaf rows are partitioned by their tree's network
     (Arena.league_route), every network evaluates its own segment, and the outputs return to arena-row order
@@ -834,12 +847,13 @@ class LeagueEngine:
     share an evaluator."""
 
     KINDS = {"random": _lib.PLAYER_RANDOM, "lookahead": _lib.PLAYER_LOOKAHEAD,
-             "onesteplookahead": _lib.PLAYER_LOOKAHEAD}
+             "onesteplookahead": _lib.PLAYER_LOOKAHEAD, "negamax": _lib.PLAYER_NEGAMAX}
 
     def __init__(self, game, players, pairings, games_per_pairing=100, seed=0, search_threads=4,
                  dtype=torch.float16, subsequence0=0, device=None, leaf_layout="nhwc", cpuct=4.0, x_noise=0.25,
-                 blocks_per_tree=0, openings=None):
-        """openings: an opening book (openings.py) with id period g, the per-pairing slot count: every pairing
+                 blocks_per_tree=0, openings=None, rng="philox"):
+        """rng: "philox", or "tape" (every tree draws from its own given stream: Arena.set_tapes before start()).
+        openings: an opening book (openings.py) with id period g, the per-pairing slot count: every pairing
         walks the suite from its first opening, slots 2k and 2k + 1 of a pairing play opening k mod len(openings)
         once per colour.  None = every game starts on the empty board."""
         self.game = game
@@ -859,7 +873,9 @@ class LeagueEngine:
             if p.get("network") is None:
                 kind = str(p.get("kind", "")).lower()
                 if kind not in self.KINDS:
-                    raise ValueError(f"a player needs network= or kind= random / lookahead, got {p!r}")
+                    raise ValueError(f"a player needs network= or kind= random / lookahead / negamax, got {p!r}")
+                if kind == "negamax":
+                    p["iterations"] = negamax_depth(p.get("depth", 2))  # the tree's budget is its depth
                 self.player_net.append(-1)
                 continue
             net = p["network"]
@@ -886,7 +902,7 @@ class LeagueEngine:
         its = [int(p.get("iterations", 100)) for p in mcts] or [1]
         ks = [max(1, int(p.get("search_threads", K0))) for p in mcts] or [K0]
         self.iterations = max(its)
-        self.arena = a = Arena(game, n_trees=2 * n, n_games=n, iterations=self.iterations, seed=seed,
+        self.arena = a = Arena(game, n_trees=2 * n, n_games=n, iterations=self.iterations, seed=seed, rng=rng,
                                subsequence0=subsequence0, evaluate=True, leaf_format=fmt, leaf_layout=layout,
                                cpuct=cpuct, x_noise=x_noise, blocks_per_tree=blocks_per_tree, device=self.device,
                                search_threads=max(ks))

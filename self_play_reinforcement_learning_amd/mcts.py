@@ -313,3 +313,109 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
     finally:
         arena.close()
     return out
+
+
+SOLVE_ILLEGAL = -128  # the code of an illegal move (include/spmcts.h "exact depth-limited negamax")
+
+
+def solve_positions(game, positions=None, boards=None, players=None, depth=6, device=None):
+    """The truth about a batch of positions, to a horizon: the exact depth-limited negamax on the device
+    (include/spmcts.h spmcts_negamax_batch; no network, no arena).
+
+    positions: move lists from the empty board (validated like an opening book: legal, not ending the game),
+    player 1 first, so the mover is 1 after an even number of moves and -1 after an odd one.  Or boards int8
+    [n, W, H] of +-1 stones with players [n], the side to move of each; a board is assumed not to be finished
+    (one that already holds a line is searched as if play went on).  depth: 1 .. 8 on the Connect4 boards, 1 .. 9
+    on TicTacToe (a full solve).
+
+    Returns device tensors: score int8 [n, A], one code per action -- +k (k odd): playing it forces a win within
+    k plies and not sooner (the move itself is ply 1); -k (k even): every line loses, k the latest ply the loss can
+    be delayed to; 0: not decided within `depth` plies (a full-board draw too); -128: illegal.  The better move has
+    the higher place in +1 > +3 > ... > 0 > ... > -4 > -2.  value int8 [n]: the best code over the legal moves (0
+    where there is none); best bool [n, A]: the legal moves that carry it; nodes int64 [n]: moves the search made.
+
+    The search's own answer held against it (tactical_report below):
+        tactical_report(solve_positions(game, seqs)["score"], analyse_positions(game, net, seqs, 200)["action"])"""
+    from . import _lib
+    from .arena import GAMES, _stream
+    from .hardcoded_players import negamax_max_depth, negamax_rank
+    from .openings import validate_openings
+
+    game = game if isinstance(game, str) else game_of_env(game)
+    gid, W, H, A = GAMES[game]
+    cap = negamax_max_depth(game)
+    if isinstance(depth, bool) or not isinstance(depth, int) or not 1 <= depth <= cap:
+        raise ValueError(f"depth must be an integer in [1, {cap}] on {game}, got {depth!r}")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if (positions is None) == (boards is None):
+        raise ValueError("solve_positions takes either positions= (move lists) or boards= with players=")
+    if positions is not None:
+        from .envs import Connect4Env, TicTacToeEnv
+
+        seqs = validate_openings(game, positions)
+        env = TicTacToeEnv() if game == "tictactoe" else Connect4Env(W, H)
+        bs = np.zeros((len(seqs), W, H), dtype=np.int8)
+        for i, seq in enumerate(seqs):
+            env.reset()
+            for p, a in enumerate(seq):
+                env.step(a, 1 if p % 2 == 0 else -1)
+            bs[i] = env.board
+        boards = torch.as_tensor(bs)
+        players = torch.as_tensor(np.array([1 if len(s) % 2 == 0 else -1 for s in seqs], dtype=np.int8))
+    elif players is None:
+        raise ValueError("boards= needs players= (the side to move of each board)")
+    b = torch.as_tensor(boards).to(dev, torch.int8).reshape(-1, W, H).contiguous()
+    pl = torch.as_tensor(players).to(dev, torch.int8).reshape(-1).contiguous()
+    n = b.shape[0]
+    if pl.shape[0] != n:
+        raise ValueError(f"{n} boards but {pl.shape[0]} players")
+    score = torch.full((n, A), SOLVE_ILLEGAL, dtype=torch.int8, device=dev)
+    nodes = torch.zeros(n, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("spmcts_negamax_batch", gid, W, H, _lib.ptr(b), _lib.ptr(pl), n, depth, _lib.ptr(score),
+                  _lib.ptr(nodes), _stream())
+    rank = negamax_rank(score)
+    top = rank.max(dim=1, keepdim=True).values if n else rank[:, :1]
+    legal = score != SOLVE_ILLEGAL
+    best = (rank == top) & legal
+    value = torch.where(legal.any(dim=1), (score.long() * best).sum(dim=1) // best.sum(dim=1).clamp(min=1),
+                        torch.zeros(n, dtype=torch.int64, device=dev)).to(torch.int8)
+    return dict(score=score, value=value, best=best, nodes=nodes)
+
+
+TACTICAL_CLASSES = ("missed_win", "slower_win", "blunder", "forced_loss", "ok")
+
+
+def tactical_report(score, action):
+    """Each position's chosen move held against its exact codes (solve_positions(...)["score"], int8 [n, A];
+    action [n]).  Pure torch.  One class per position, the first that applies:
+        missed_win   a +k existed and the chosen code is <= 0
+        slower_win   the chosen move wins, but a faster win existed
+        blunder      the chosen code is < 0 while a code >= 0 existed
+        forced_loss  every legal code is < 0
+        ok           anything else
+    Returns {"label": [n names], "class": int64 [n] (index into TACTICAL_CLASSES), "chosen": int8 [n] (the chosen
+    moves' codes), "counts": {name: count}}.  ValueError if a chosen move is illegal."""
+    score = torch.as_tensor(score)
+    action = torch.as_tensor(action).to(score.device, torch.int64).reshape(-1)
+    n = score.shape[0]
+    if action.shape[0] != n:
+        raise ValueError(f"{n} score rows but {action.shape[0]} actions")
+    s = score.long()
+    chosen = s.gather(1, action.reshape(-1, 1)).reshape(-1) if n else s.reshape(-1)[:0]
+    if bool((chosen == SOLVE_ILLEGAL).any()):
+        raise ValueError("a chosen move is illegal (code -128)")
+    legal = s != SOLVE_ILLEGAL
+    big = torch.full_like(s, 1 << 20)
+    fastest = torch.where(s > 0, s, big).min(dim=1).values if n else chosen  # the smallest +k (1 << 20: none)
+    has_win = fastest < (1 << 20)
+    safe = ((s >= 0) & legal).any(dim=1) if n else chosen > 0
+    cls = torch.full((n,), TACTICAL_CLASSES.index("ok"), dtype=torch.int64, device=score.device)
+    # assigned from the last rule to the first, so the first that applies stands
+    cls[~safe] = TACTICAL_CLASSES.index("forced_loss")
+    cls[(chosen < 0) & safe] = TACTICAL_CLASSES.index("blunder")
+    cls[has_win & (chosen > fastest)] = TACTICAL_CLASSES.index("slower_win")
+    cls[has_win & (chosen <= 0)] = TACTICAL_CLASSES.index("missed_win")
+    label = [TACTICAL_CLASSES[i] for i in cls.tolist()]
+    return {"label": label, "class": cls, "chosen": chosen.to(torch.int8),
+            "counts": {name: label.count(name) for name in TACTICAL_CLASSES}}

@@ -408,6 +408,8 @@ class SelfPlayScheduler:
         name = getattr(gen, "__name__", "").lower()
         if name in ("random", "onesteplookahead"):
             return ("random" if name == "random" else "lookahead"), {}
+        if name == "negamax":  # its depth is the container's, or the player's default
+            return "negamax", {"opponent_depth": int((getattr(c, "policy_kwargs", {}) or {}).get("depth", 2))}
         kw = dict(getattr(c, "policy_kwargs", {}) or {})
         net = self.evaluation_network
         if net is None:
