@@ -399,6 +399,47 @@ int spmcts_negamax_host(int32_t game, int32_t width, int32_t height, const int8_
 int spmcts_negamax_batch(int32_t game, int32_t width, int32_t height, const int8_t *boards_dev,
                          const int8_t *players_dev, int32_t n, int32_t depth, int8_t *scores_dev, uint64_t *nodes_dev,
                          spmcts_stream stream);
+/* ---- exact solver to the end of the game (csrc/solve.h) ---------------------------------------------------------
+ * An alpha-beta search with a transposition table that runs every line to the end of the game.  A root move's
+ * code is what spmcts_negamax_* would give at any depth D >= the number of empty cells:
+ *   +k    playing it, the mover forces a win in k plies and not sooner (the move is ply 1)
+ *   -k    every line loses by force; k = the latest ply the loss can be delayed to
+ *    0    a draw under best play (nothing is undecided)
+ *   -128  an illegal move
+ *   -127  a legal move whose search gave up at the node budget (never a guess)
+ * Equivalently s(pos) = the maximum over the legal moves of e if the move wins, 0 if it fills the board, -s(child)
+ * otherwise, e = the empty cells of pos; the code of a move with value s is e + 1 - s, -(e + 1 + s) or 0.
+ * The position must be unfinished and hold no line of L for either side: -3 otherwise.
+ * The table is the caller's: uint64 entries, zeroed (0 = empty), a power-of-two count >= 2^16, for one board only;
+ * it may be kept across calls and shared by a batch (an entry is a truth about a position: a hit proves the
+ * position's identity bit for bit, one entry is one 64-bit load or store).  max_nodes >= 1 is a position's budget
+ * of moves made (nodes); a position that reaches it stops: the moves it has not finished get -127, what it
+ * finished stays exact, nothing unfinished is stored in the table.  A move that wins at once or fills the board
+ * needs no search and keeps its code under any budget. */
+/* Host twin (the kernels' search core compiled for the host; no GPU): a host table; board int8 [W][H] of +-1
+ * stones, player = the side to move; scores int8 [A], nodes (may be NULL): the moves made.  The root's own moves are
+ * always made (A at the most); past them a move is made only while the count is below max_nodes. */
+int spmcts_solve_host(int32_t game, int32_t width, int32_t height, const int8_t *board /*[W][H]*/, int32_t player,
+                      uint64_t *table, uint64_t table_entries, uint64_t max_nodes, int8_t *scores /*[A]*/,
+                      uint64_t *nodes);
+/* The bytes of spmcts_solve_batch's work buffer for n positions (A * A parked searches each). */
+int spmcts_solve_work_bytes(int32_t game, int32_t width, int32_t height, int32_t n, uint64_t *bytes_out);
+/* n positions on the device: boards_dev int8 [n][W][H], players_dev int8 [n], table_dev uint64 [table_entries],
+ * work_dev (spmcts_solve_work_bytes; contents arbitrary) -> scores_dev int8 [n][A], nodes_dev uint64 [n] (may be
+ * NULL).  One lane per (position, first move, second move); a launch gives every running lane at most
+ * launch_nodes steps of at most one move each (0: the default, csrc/spmcts.hip SV_LAUNCH_STEPS; else >= 4), a lane
+ * that is not through parks its stack in work_dev and the next launch resumes it there.  Synchronous: the count
+ * of running lanes is read back after every launch; a position whose lanes have made max_nodes moves is given up
+ * at the next launch (so it may overshoot by its lanes' last slices).  n = 0 is a no-op; -3 with a
+ * spmcts_last_error text for a bad table size, max_nodes = 0, a launch_nodes of 1 .. 3 or a finished position.
+ * The codes of solved positions are bit-equal to the host twin's (both are exact); node counts depend on the
+ * table's contents and on the lanes that share it. */
+int spmcts_solve_batch(int32_t game, int32_t width, int32_t height, const int8_t *boards_dev,
+                       const int8_t *players_dev, int32_t n, uint64_t *table_dev, uint64_t table_entries,
+                       void *work_dev, uint64_t max_nodes, uint32_t launch_nodes, int8_t *scores_dev,
+                       uint64_t *nodes_dev, spmcts_stream stream);
+/* The step launches of this thread's last spmcts_solve_batch. */
+int spmcts_solve_launches(void);
 /* Deterministic table network (oracle/table_net.py) over leaf rows, for bit-exact
  * search parity tests: leaves in any spmcts_leaf_format/layout; per-row salts optional. */
 int spmcts_table_net(int32_t game, int32_t width, int32_t height, const void *leaves_dev, int32_t leaf_format,

@@ -13,7 +13,9 @@ Public API mirrors the reference:
     Elo, ModelDatabase                    (games/algos/elo.py, games/algos/model_database.py)
 plus the arena itself: Arena, SelfPlayEngine, LanedEngine, LeagueEngine, DeviceTableNet, and what the reference
 has no form of: opening books (openings.py: enumerate_openings, validate_openings), analyse_positions, and the
-exact depth-limited solver (solve_positions, tactical_report).
+exact depth-limited solver (solve_positions, tactical_report), and the exact solver to the end of the game
+(solve.py: SolveTable, solve_to_end, perfect_report) with the reference's PerfectEvaluator
+(games/algos/evaluation_worker.py) on top of it.
 """
 from .base_model import BasePlayer, ModelContainer, Policy, TrainableModel  # noqa: F401
 from .memory import Memory  # noqa: F401
@@ -33,6 +35,10 @@ _LAZY = {
     "analyse_positions": ".mcts",
     "solve_positions": ".mcts",
     "tactical_report": ".mcts",
+    "SolveTable": ".solve",
+    "solve_to_end": ".solve",
+    "perfect_report": ".solve",
+    "PerfectEvaluator": ".evaluation_worker",
     "enumerate_openings": ".openings",
     "validate_openings": ".openings",
     "SelfPlayScheduler": ".self_play_parallel",

@@ -136,6 +136,10 @@ _SIGS = {
     "spmcts_negamax_launch_positions": [_I32, _I32, _I32, _I32],
     "spmcts_negamax_host": [_I32, _I32, _I32, _P, _I32, _I32, _P, ctypes.POINTER(_U64)],
     "spmcts_negamax_batch": [_I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P],
+    "spmcts_solve_host": [_I32, _I32, _I32, _P, _I32, _P, _U64, _U64, _P, ctypes.POINTER(_U64)],
+    "spmcts_solve_work_bytes": [_I32, _I32, _I32, _I32, ctypes.POINTER(_U64)],
+    "spmcts_solve_batch": [_I32, _I32, _I32, _P, _P, _I32, _P, _U64, _P, _U64, ctypes.c_uint32, _P, _P, _P],
+    "spmcts_solve_launches": [],
     "spmcts_table_net": [_I32, _I32, _I32, _P, _I32, _I32, _I32, _U64, _P, _P, _P, _P],
     "spmcts_set_leaf_dedup": [_P, _I32],
     "spmcts_set_leaf_peer": [_P, _P],

@@ -32,6 +32,7 @@
 //   arena_rows.h    leaf dedup, evaluation cache, peer push, k_scan_need, k_encode
 //   arena_expand.h  k_expand, threaded expand and select (one slot-cycle walk), _play, k_search_end, set_node, k_play_action
 //   negamax.h       exact depth-limited negamax: the search core (host and device), its batch and arena kernels
+//   solve.h         exact solver to the end of the game: alpha-beta with a transposition table, resumable launches
 //   arena_games.h   game state machine (opening book plies included), the hard-coded players, k_root_stats_batch, export
 //   arena_misc.h    k_env_step, k_table_net, k_copy_probe, the init kernels
 //   arena_league.h  league routing: a step's rows partitioned by their tree's network, and back
@@ -89,6 +90,7 @@ static int fail(int code, const std::string &msg) {
 #include "arena_rows.h"
 #include "arena_expand.h"
 #include "negamax.h"
+#include "solve.h"
 #include "arena_games.h"
 #include "arena_misc.h"
 #include "arena_league.h"
@@ -397,6 +399,24 @@ static int negamax_games(spmcts_arena *h, hipStream_t s) {
                     h->v, (int)g0, n);
     });
   });
+}
+
+// ---- solver launches -----------------------------------------------------------
+// A launch of spmcts_solve_batch gives every running item at most SV_LAUNCH_STEPS steps of sv_iter, each at most
+// one move (csrc/solve.h); an item that is not through parks and the next launch resumes it.
+// Measured on one MI355X (DESIGN.md §4 "Exact solver to the end of the game", profiles/solve/): 4,096 positions of
+// 7x6 after 20 random plies, 1.33e9 moves in 1.476 s = 9.0e8 nodes/s over 17 launches of 65,536 steps, 87 ms per
+// launch on average (the full first launches of 200,704 lanes and the tail's few lanes are in that mean; they were
+// not timed apart): a lane takes about 7.5e5 steps/s.  At that rate a launch of 2^16 steps takes 0.09 s, and stays
+// under a second with lanes ten times slower.
+static const uint32_t SV_LAUNCH_STEPS = 1u << 16;
+static thread_local int g_solve_launches = 0;
+
+static int sv_table_check(const void *table, uint64_t entries) {
+  if (!table) return fail(-1, "null argument");
+  if (entries < (1ull << SV_MIN_TABLE_BITS) || (entries & (entries - 1)))
+    return fail(-3, "solve table: a power-of-two number of entries, at least 2^16");
+  return 0;
 }
 
 extern "C" {
@@ -1317,6 +1337,77 @@ int spmcts_negamax_batch(int32_t game, int32_t width, int32_t height, const int8
       return launch(k_negamax_batch<G>, ((long long)m + NmGrid<G>::PPB - 1) / NmGrid<G>::PPB * NM_THREADS, NM_THREADS,
                     (hipStream_t)stream, boards_dev, players_dev, p0, m, depth, scores_dev, nodes_dev);
     });
+  });
+}
+
+// ---- exact solver to the end of the game -------------------------------------------
+int spmcts_solve_host(int32_t game, int32_t width, int32_t height, const int8_t *board, int32_t player, uint64_t *table,
+                      uint64_t table_entries, uint64_t max_nodes, int8_t *scores, uint64_t *nodes) {
+  return with_game(game, width, height, [&](auto g) {
+    using G = decltype(g);
+    if (!board || !scores) return fail(-1, "null argument");
+    TRY(sv_table_check(table, table_entries));
+    if (max_nodes < 1) return fail(-3, "max_nodes must be at least 1");
+    const Board b = from_cells<G>(board);
+    if (popc(b.pos | b.neg) == G::CELLS) return fail(-3, "the position is finished: the board is full");
+    if (sv_has_line<G>(b.pos) || sv_has_line<G>(b.neg)) return fail(-3, "the position is finished: the board holds a line");
+    sv_solve_host<G>(player > 0 ? b.pos : b.neg, player > 0 ? b.neg : b.pos, table, table_entries - 1, max_nodes, scores,
+                     nodes);
+    return 0;
+  });
+}
+
+int spmcts_solve_work_bytes(int32_t game, int32_t width, int32_t height, int32_t n, uint64_t *bytes_out) {
+  return with_game(game, width, height, [&](auto g) {
+    if (!bytes_out) return fail(-1, "null argument");
+    if (n < 0) return fail(-3, "n must not be negative");
+    *bytes_out = (uint64_t)sv_work_bytes<decltype(g)>(n);
+    return 0;
+  });
+}
+
+int spmcts_solve_launches(void) { return g_solve_launches; }
+
+int spmcts_solve_batch(int32_t game, int32_t width, int32_t height, const int8_t *boards_dev, const int8_t *players_dev,
+                       int32_t n, uint64_t *table_dev, uint64_t table_entries, void *work_dev, uint64_t max_nodes,
+                       uint32_t launch_nodes, int8_t *scores_dev, uint64_t *nodes_dev, spmcts_stream stream) {
+  return with_game(game, width, height, [&](auto g) {
+    using G = decltype(g);
+    g_solve_launches = 0;
+    if (n < 0) return fail(-3, "n must not be negative");
+    if (max_nodes < 1) return fail(-3, "max_nodes must be at least 1");
+    if (launch_nodes != 0 && launch_nodes < 4) return fail(-3, "launch_nodes: 0 (the default slice) or at least 4");
+    if (table_entries < (1ull << SV_MIN_TABLE_BITS) || (table_entries & (table_entries - 1)))
+      return fail(-3, "solve table: a power-of-two number of entries, at least 2^16");
+    if (n == 0) return 0;
+    if (!boards_dev || !players_dev || !scores_dev || !table_dev || !work_dev) return fail(-1, "null argument");
+    const hipStream_t s = (hipStream_t)stream;
+    const uint32_t slice = launch_nodes ? launch_nodes : SV_LAUNCH_STEPS;
+    const SvWork w = sv_work<G>(work_dev, n);
+    const uint64_t tmask = table_entries - 1;
+    uint32_t head[4] = {0, 0, 0xffffffffu, 0};
+    HIP_TRY(hipMemsetAsync(work_dev, 0, 16 + (size_t)n * 8, s));
+    HIP_TRY(hipMemcpyAsync(work_dev, head, sizeof(head), hipMemcpyHostToDevice, s));
+    TRY(launch(k_solve_init<G>, w.N, SV_THREADS, s, boards_dev, players_dev, w, table_dev, tmask));
+    HIP_TRY(hipMemcpyAsync(head, work_dev, sizeof(head), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (head[1])
+      return fail(-3, "position " + std::to_string(head[2]) + " is finished (a full board or a line): " +
+                          std::to_string(head[1]) + " such in the batch");
+    // a launch with an item still running makes at least (slice - 1) / 2 moves for that item's position (a step
+    // that makes no move pops a level a move pushed), so the budget ends the loop
+    const uint64_t max_launches = max_nodes / ((slice - 1) / 2) + 2;
+    for (uint64_t l = 0; l < max_launches; ++l) {
+      HIP_TRY(hipMemsetAsync(work_dev, 0, 4, s));
+      TRY(launch(k_solve_step<G>, w.N, SV_THREADS, s, w, table_dev, tmask, max_nodes, slice));
+      HIP_TRY(hipMemcpyAsync(head, work_dev, 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      ++g_solve_launches;
+      if (head[0] == 0) break;
+    }
+    TRY(launch(k_solve_fold<G>, n, SV_THREADS, s, boards_dev, w, n, scores_dev, nodes_dev));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
   });
 }
 

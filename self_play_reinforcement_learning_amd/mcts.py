@@ -88,6 +88,7 @@ class MCTreeSearch(Policy):
         self.optim = optim
         self.iterations = iterations
         self.alpha = alpha
+        self.cpuct, self.x_noise = cpuct, x_noise  # (read back by PerfectEvaluator's batch search)
         self.strong_play = strong_play
         self.q_average = q_average
         self.batch_size = batch_size
