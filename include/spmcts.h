@@ -293,6 +293,25 @@ int spmcts_games_finish_ply(spmcts_arena *h, int32_t refill, int32_t *out_dev /*
 int spmcts_export_moves(spmcts_arena *h, int8_t *states_dev, float *tree_probs_dev, double *q_dev, uint8_t *q_f64_dev,
                         float *z_dev, int64_t *game_dev, int32_t max_records, int32_t *count_dev,
                         spmcts_stream stream);
+/* The game log: with `on`, every ply of every game (searched moves, the hard-coded players' moves, opening-book
+ * plies) stores its action in the slot's log, uint8 [n_games][W*H], and spmcts_games_finish_ply puts each finished
+ * game's record into the finished-game ring before the slot is reused: game id i64, slot i32, result i8 (tree 2g's
+ * view, the value spmcts_games_results gives), swap u8, plies i32, opening i32 (-1 without a book), moves u8 [W*H]
+ * (bytes past `plies` zero).  A ply's records lie in slot order after those already in the ring (no atomics: the
+ * layout is the same on every run).  The ring holds 2 * n_games records, the games two plies can finish: drained
+ * once per ply (spmcts_export_games) it never fills.  A record that does not fit is dropped whole, with
+ * SPMCTS_ERR_EXPORT raised; nothing is overwritten.  The first `on` allocates the log and the ring (n_games * W*H
+ * bytes + 2 * n_games * (22 + W*H) bytes, outside spmcts_arena_bytes, as the evaluation cache's memory is); an
+ * arena that never calls this allocates nothing and its kernels see a null log.  The log changes no search, random
+ * draw, Move record or result.  Refused (-4) while any game slot is active.  (sync) */
+int spmcts_games_set_log(spmcts_arena *h, int32_t on);
+/* Copy the finished-game ring out (at most max_records records, the fields of spmcts_games_set_log one array
+ * each) and clear it; count_dev[0] = records copied.  The twin of spmcts_export_moves: no host synchronisation.
+ * Like it, the call empties the whole ring: with max_records below the ring's count the records past max_records
+ * are discarded without a flag, so pass the ring's capacity, 2 * n_games, to lose none. */
+int spmcts_export_games(spmcts_arena *h, int64_t *id_dev, int32_t *slot_dev, int8_t *result_dev, uint8_t *swap_dev,
+                        int32_t *plies_dev, int32_t *opening_dev, uint8_t *moves_dev, int32_t max_records,
+                        int32_t *count_dev, spmcts_stream stream);
 /* (sync) per-slot game state: active flag, ply, swap, game id */
 int spmcts_games_state(spmcts_arena *h, uint8_t *active, int32_t *ply, uint8_t *swap, int64_t *game_id);
 
@@ -440,6 +459,25 @@ int spmcts_solve_batch(int32_t game, int32_t width, int32_t height, const int8_t
                        uint64_t *nodes_dev, spmcts_stream stream);
 /* The step launches of this thread's last spmcts_solve_batch. */
 int spmcts_solve_launches(void);
+/* ---- game records: from move lists to the positions before their moves (csrc/records.h; no arena) ----------- */
+/* moves u8 [n][W*H] and plies i32 [n]: n game records (spmcts_export_games' fields, or any move lists from the
+ * empty board).  Each record is replayed with the rules of spmcts_env_step_host, the first mover's stones +1 and
+ * the mover +1 on even plies, -1 on odd ones.  status u8 [n]: 0 legal; 1 an illegal move (outside the action
+ * range, a full column, an occupied TicTacToe cell); 2 a move after the game was over; 3 plies outside
+ * [0, W*H].  Every legal record gives one row per ply p in [first_ply, plies), in (record, ply) order: boards i8
+ * [N][W][H] the board before move p, players i8 [N] the side to move (the boards / players of
+ * spmcts_negamax_batch and spmcts_solve_batch), row_record and row_ply i32 [N].  offsets i32 [n + 1]: each
+ * record's first row (the exclusive scan of the legal records' row counts; no atomics, so the layout is the same
+ * on every run), offsets[n] = N.  Rows at or past max_rows are not written (sum of max(0, plies - first_ply) is
+ * always enough).  Asynchronous on `stream`; n = 0 is a no-op. */
+int spmcts_log_positions(int32_t game, int32_t width, int32_t height, const uint8_t *moves_dev, const int32_t *plies_dev,
+                         int32_t n, int32_t first_ply, int32_t max_rows, int8_t *boards_dev, int8_t *players_dev,
+                         int32_t *row_record_dev, int32_t *row_ply_dev, uint8_t *status_dev, int32_t *offsets_dev,
+                         spmcts_stream stream);
+/* The host twin (the same core compiled for the host; no GPU): host pointers, every output bit-equal. */
+int spmcts_log_positions_host(int32_t game, int32_t width, int32_t height, const uint8_t *moves, const int32_t *plies,
+                              int32_t n, int32_t first_ply, int32_t max_rows, int8_t *boards, int8_t *players,
+                              int32_t *row_record, int32_t *row_ply, uint8_t *status, int32_t *offsets);
 /* Deterministic table network (oracle/table_net.py) over leaf rows, for bit-exact
  * search parity tests: leaves in any spmcts_leaf_format/layout; per-row salts optional. */
 int spmcts_table_net(int32_t game, int32_t width, int32_t height, const void *leaves_dev, int32_t leaf_format,

@@ -15,7 +15,8 @@ plus the arena itself: Arena, SelfPlayEngine, LanedEngine, LeagueEngine, DeviceT
 has no form of: opening books (openings.py: enumerate_openings, validate_openings), analyse_positions, and the
 exact depth-limited solver (solve_positions, tactical_report), and the exact solver to the end of the game
 (solve.py: SolveTable, solve_to_end, perfect_report) with the reference's PerfectEvaluator
-(games/algos/evaluation_worker.py) on top of it.
+(games/algos/evaluation_worker.py) on top of it, and game records (records.py: GameRecords, the move lists the
+arenas' games leave behind with record_games=True; grade_games, their moves held against the exact solvers).
 """
 from .base_model import BasePlayer, ModelContainer, Policy, TrainableModel  # noqa: F401
 from .memory import Memory  # noqa: F401
@@ -39,6 +40,8 @@ _LAZY = {
     "solve_to_end": ".solve",
     "perfect_report": ".solve",
     "PerfectEvaluator": ".evaluation_worker",
+    "GameRecords": ".records",
+    "grade_games": ".records",
     "enumerate_openings": ".openings",
     "validate_openings": ".openings",
     "SelfPlayScheduler": ".self_play_parallel",

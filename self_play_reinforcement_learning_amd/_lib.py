@@ -27,7 +27,7 @@ ERR_FLAGS = {
     0x4: "select reached a node without valid children",
     0x8: "illegal action",
     0x10: "inconsistent tree state",
-    0x20: "move export ring overflow",
+    0x20: "move export ring or finished-game ring overflow",
 }
 
 
@@ -117,6 +117,8 @@ _SIGS = {
     "spmcts_games_end_ply": [_P, _P, _P, _P],
     "spmcts_games_finish_ply": [_P, _I32, _P, _P],
     "spmcts_export_moves": [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P],
+    "spmcts_games_set_log": [_P, _I32],
+    "spmcts_export_games": [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P],
     "spmcts_games_state": [_P, _P, _P, _P, _P],
     "spmcts_games_results": [_P, _P, _P, _P, _P],
     "spmcts_games_set_openings": [_P, _P, _P, _I32, _I32, _I32],
@@ -140,6 +142,8 @@ _SIGS = {
     "spmcts_solve_work_bytes": [_I32, _I32, _I32, _I32, ctypes.POINTER(_U64)],
     "spmcts_solve_batch": [_I32, _I32, _I32, _P, _P, _I32, _P, _U64, _P, _U64, ctypes.c_uint32, _P, _P, _P],
     "spmcts_solve_launches": [],
+    "spmcts_log_positions": [_I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
+    "spmcts_log_positions_host": [_I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P],
     "spmcts_table_net": [_I32, _I32, _I32, _P, _I32, _I32, _I32, _U64, _P, _P, _P, _P],
     "spmcts_set_leaf_dedup": [_P, _I32],
     "spmcts_set_leaf_peer": [_P, _P],

@@ -466,18 +466,29 @@ class Arena:
              ptr(e["z"]), ptr(e["game"]), self._exp_cap, ptr(self._exp_count), _stream())
         self._exp_host[0:2].copy_(self._finish, non_blocking=True)
         self._exp_host[2:3].copy_(self._exp_count[0:1], non_blocking=True)
+        if getattr(self, "games_log", False):  # the finished-game ring rides along: same buffers every ply, same event
+            if getattr(self, "_gexp", None) is None:
+                self._gexp = self._game_buffers(2 * self.n_games)  # the ring's capacity (spmcts_games_set_log)
+                self._gexp_count = torch.zeros(4, dtype=torch.int32, device=self.device)
+                self._gexp_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+            self._export_games_into(self._gexp, self._gexp_count)
+            self._gexp_host.copy_(self._gexp_count[0:1], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         return ev
 
     def finish_export_result(self, ev):
         """(#games finished, Move records) of finish_export_async once `ev` has completed (waits for it); the
-        records are copies (queued on the current stream), so the persistent buffers can be reused next ply."""
+        records are copies (queued on the current stream), so the persistent buffers can be reused next ply.  With
+        the game log on, the ply's finished-game records (export_games' dict) are left in `last_games`."""
         ev.synchronize()
         finished, ring, k = (int(x) for x in self._exp_host.tolist())
         if k != ring:
             raise _lib.SpmctsError(f"Move export took {k} of {ring} ring records (buffer capacity {self._exp_cap})")
         moves = {key: v[:k].clone() for key, v in self._exp.items()} if k else None
+        if getattr(self, "games_log", False):
+            g = int(self._gexp_host[0])
+            self.last_games = {key: v[:g].clone() for key, v in self._gexp.items()}
         return finished, moves
 
     def export_moves(self, max_records):
@@ -495,6 +506,40 @@ class Arena:
              ptr(out["q_f64"]), ptr(out["z"]), ptr(out["game"]), n, ptr(self._count), _stream())
         k = self._read_count()
         return {key: v[:k] for key, v in out.items()}
+
+    def games_set_log(self, on=True):
+        """The game log (include/spmcts.h spmcts_games_set_log): every ply's action is kept per slot and each
+        finished game leaves a record in the finished-game ring (export_games).  Raises while a game is active."""
+        torch.cuda.current_stream().synchronize()
+        call("spmcts_games_set_log", self.h, int(bool(on)))
+        self.games_log = bool(on)
+
+    def export_games(self, n=None):
+        """The finished-game ring as a dict of device tensors, one per field, and the ring cleared (include/spmcts.h
+        spmcts_export_games): id int64 [k], slot int32 [k], result int8 [k] (tree 2g's view), swap uint8 [k], plies
+        int32 [k], opening int32 [k] (-1 without a book), moves uint8 [k, W*H] (bytes past plies zero).  At most `n`
+        records (None: the ring's capacity, 2 * n_games).  The call empties the whole ring: records past `n` are
+        discarded, so an `n` below the capacity is for callers that know fewer are there."""
+        out = self._game_buffers(max(1, 2 * self.n_games if n is None else int(n)))
+        self._export_games_into(out, self._count)
+        k = self._read_count()
+        return {key: v[:k] for key, v in out.items()}
+
+    def _game_buffers(self, n):
+        dev = self.device
+        return dict(
+            id=torch.zeros(n, dtype=torch.int64, device=dev),
+            slot=torch.zeros(n, dtype=torch.int32, device=dev),
+            result=torch.zeros(n, dtype=torch.int8, device=dev),
+            swap=torch.zeros(n, dtype=torch.uint8, device=dev),
+            plies=torch.zeros(n, dtype=torch.int32, device=dev),
+            opening=torch.zeros(n, dtype=torch.int32, device=dev),
+            moves=torch.zeros((n, self.cells), dtype=torch.uint8, device=dev),
+        )
+
+    def _export_games_into(self, out, count):
+        call("spmcts_export_games", self.h, ptr(out["id"]), ptr(out["slot"]), ptr(out["result"]), ptr(out["swap"]),
+             ptr(out["plies"]), ptr(out["opening"]), ptr(out["moves"]), int(out["id"].shape[0]), ptr(count), _stream())
 
     def games_state(self):
         G = self.n_games

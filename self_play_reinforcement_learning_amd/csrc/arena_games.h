@@ -162,6 +162,8 @@ __global__ void k_games_end_ply(View v) {
   if (book && (o.action >= G::A || !((legal_mask<G>(gb) >> o.action) & 1u))) set_err(v, SPMCTS_ERR_ACTION);
   const int st = step<G>(gb, o.action, p_env, &rew, &done);
   if (st != STEP_OK) set_err(v, SPMCTS_ERR_ACTION);
+  // the game log (spmcts_games_set_log): every ply's action, whoever chose it (a game has at most CELLS plies)
+  if (v.glog && v.gply[g] < G::CELLS) v.glog[(size_t)g * G::CELLS + v.gply[g]] = (uint8_t)o.action;
   v.gpos[g] = gb.pos;
   v.gneg[g] = gb.neg;
   v.gply[g] += 1;
@@ -234,6 +236,12 @@ __global__ __launch_bounds__(1024) void k_games_finish_scan(View v, int refill, 
     if (base_rec + total_rec > v.ex_cap) atomicOr(v.err, SPMCTS_ERR_EXPORT);
     v.ex_count[0] = min(v.ex_cap, base_rec + total_rec);
     v.gcnt[9] += min(total_rec, v.ex_cap - base_rec);
+    if (v.glog) {  // the finished-game ring: game g's record goes to base + its finish index (k_games_finish_apply)
+      const int base_log = v.lr_count[0];
+      v.gscratch[2 * Gn + 4] = base_log;
+      if (base_log + total_fin > v.lr_cap) atomicOr(v.err, SPMCTS_ERR_EXPORT);  // the records past the end are dropped whole
+      v.lr_count[0] = min(v.lr_cap, base_log + total_fin);
+    }
     if (out) {
       out[0] = total_fin;
       out[1] = v.ex_count[0];
@@ -269,6 +277,20 @@ __global__ void k_games_finish_apply(View v) {
   }
   const int fin_idx = v.gscratch[2 * g + 1];
   const int can = v.gscratch[2 * v.G];
+  if (v.glog) {  // the game's record, before start_game reuses the slot
+    const int at = v.gscratch[2 * v.G + 4] + fin_idx;
+    if (at < v.lr_cap) {
+      const int plies = min(v.gply[g], (int)G::CELLS);
+      v.lr_id[at] = v.gid[g];
+      v.lr_slot[at] = g;
+      v.lr_result[at] = (int8_t)r;
+      v.lr_swap[at] = (uint8_t)swap;
+      v.lr_plies[at] = plies;
+      v.lr_open[at] = v.book_n ? v.gopen[g] : -1;
+      for (int c = 0; c < G::CELLS; ++c)
+        v.lr_moves[(size_t)at * G::CELLS + c] = c < plies ? v.glog[(size_t)g * G::CELLS + c] : (uint8_t)0;
+    }
+  }
   const int64_t started = ((const int64_t *)(v.gscratch + 2 * v.G + 2))[0];
   if (fin_idx < can) {
     start_game<G>(v, g, started + fin_idx, nullptr);
@@ -326,3 +348,21 @@ __global__ void k_export(View v, int A, int cells, int8_t *st, float *pr, double
 }
 
 __global__ void k_export_clear(View v) { v.ex_count[0] = 0; }
+
+// the finished-game ring (spmcts_games_set_log) out to the caller's arrays, one per field: the twin of k_export
+__global__ void k_export_games(View v, int cells, int64_t *id, int32_t *slot, int8_t *result, uint8_t *swap, int32_t *plies,
+                               int32_t *opening, uint8_t *moves, int max_records, int32_t *count_out) {
+  const int n = min(v.lr_count[0], max_records);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0 && count_out) count_out[0] = n;
+  if (i >= n) return;
+  id[i] = v.lr_id[i];
+  slot[i] = v.lr_slot[i];
+  result[i] = v.lr_result[i];
+  swap[i] = v.lr_swap[i];
+  plies[i] = v.lr_plies[i];
+  opening[i] = v.lr_open[i];
+  for (int c = 0; c < cells; ++c) moves[(size_t)i * cells + c] = v.lr_moves[(size_t)i * cells + c];
+}
+
+__global__ void k_export_games_clear(View v) { v.lr_count[0] = 0; }

@@ -128,6 +128,19 @@ struct View {
   // negamax players (SPMCTS_PLAYER_NEGAMAX, negamax.h): the codes of each tree's moves for the ply, int8 [T][A],
   // written by k_negamax_games before k_games_end_ply reads them; null until a tree of the kind is set
   int8_t *nm_score;
+  // game log (spmcts_games_set_log; null = off, the one pointer the game kernels test): glog uint8 [G][cells], the
+  // action of every ply of the slot's current game (k_games_end_ply), and the finished-game ring of lr_cap records
+  // (k_games_finish_scan / _apply -> spmcts_export_games), one array per field; lr_count[0] = records in the ring
+  uint8_t *glog;
+  int32_t lr_cap;
+  int32_t *lr_count;
+  int64_t *lr_id;
+  int32_t *lr_slot;
+  int8_t *lr_result;  // in tree 2g's view (gresult)
+  uint8_t *lr_swap;
+  int32_t *lr_plies;
+  int32_t *lr_open;   // the game's opening, -1 without a book
+  uint8_t *lr_moves;  // [lr_cap][cells], bytes past plies zero
 };
 
 enum { BOOK_MAX_OPENINGS = 65536 };

@@ -34,6 +34,7 @@
 //   negamax.h       exact depth-limited negamax: the search core (host and device), its batch and arena kernels
 //   solve.h         exact solver to the end of the game: alpha-beta with a transposition table, resumable launches
 //   arena_games.h   game state machine (opening book plies included), the hard-coded players, k_root_stats_batch, export
+//   records.h       game records (move lists) to the positions before their moves: spmcts_log_positions and its host twin
 //   arena_misc.h    k_env_step, k_table_net, k_copy_probe, the init kernels
 //   arena_league.h  league routing: a step's rows partitioned by their tree's network, and back
 //
@@ -92,6 +93,7 @@ static int fail(int code, const std::string &msg) {
 #include "negamax.h"
 #include "solve.h"
 #include "arena_games.h"
+#include "records.h"
 #include "arena_misc.h"
 #include "arena_league.h"
 
@@ -136,6 +138,10 @@ struct spmcts_arena {
   void *nm_alloc = nullptr;
   bool nm_on = false;
   int nm_depth = 0;
+  // game log (spmcts_games_set_log): the log's and the finished-game ring's allocations, kept while the log is
+  // off (View::glog null), and the log's address for turning it on again
+  std::vector<void *> log_allocs;
+  uint8_t *log_dev = nullptr;
 };
 
 static bool league_on(const spmcts_arena *h) { return h->lg.n > 0; }
@@ -495,6 +501,7 @@ int spmcts_arena_destroy(spmcts_arena *h) {
   for (void *p : h->cache_allocs) (void)hipFree(p);
   for (void *p : h->league_allocs) (void)hipFree(p);
   if (h->nm_alloc) (void)hipFree(h->nm_alloc);
+  for (void *p : h->log_allocs) (void)hipFree(p);
   delete h;
   return 0;
 }
@@ -896,6 +903,52 @@ int spmcts_games_set_record(spmcts_arena *h, int32_t record) {
   return 0;
 }
 
+int spmcts_games_set_log(spmcts_arena *h, int32_t on) {
+  if (!h) return fail(-1, "null arena");
+  if (h->v.G <= 0) return fail(-4, "arena has no game slots");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t G = h->v.G, cells = h->cells;
+  std::vector<uint8_t> st(G);
+  HIP_TRY(hipMemcpy(st.data(), h->v.gstate, G, hipMemcpyDeviceToHost));
+  for (uint8_t s : st)
+    if (s != GS_IDLE) return fail(-4, "the game log cannot change while a game is active");
+  View &v = h->v;
+  if (!on) {
+    v.glog = nullptr;
+    return 0;
+  }
+  if (h->log_allocs.empty()) {
+    // the ring holds the games of two plies (a ply finishes at most n_games): drained once per ply it never fills
+    const size_t cap = 2 * G;
+    const size_t bytes[9] = {G * cells, 16, 8 * cap, 4 * cap, cap, cap, 4 * cap, 4 * cap, cap * cells};
+    void *p[9] = {};
+    for (int i = 0; i < 9; ++i) {
+      hipError_t e = hipMalloc(&p[i], bytes[i]);
+      if (e == hipSuccess) e = hipMemset(p[i], 0, bytes[i]);
+      if (e != hipSuccess) {
+        for (int j = 0; j <= i; ++j)
+          if (p[j]) (void)hipFree(p[j]);
+        return fail(-1000 - (int)e, std::string("game log hipMalloc: ") + hipGetErrorString(e));
+      }
+    }
+    h->log_allocs.assign(p, p + 9);
+    h->log_dev = (uint8_t *)p[0];
+    v.lr_cap = (int32_t)cap;
+    v.lr_count = (int32_t *)p[1];
+    v.lr_id = (int64_t *)p[2];
+    v.lr_slot = (int32_t *)p[3];
+    v.lr_result = (int8_t *)p[4];
+    v.lr_swap = (uint8_t *)p[5];
+    v.lr_plies = (int32_t *)p[6];
+    v.lr_open = (int32_t *)p[7];
+    v.lr_moves = (uint8_t *)p[8];
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  v.glog = h->log_dev;
+  return 0;
+}
+
 int spmcts_search_end(spmcts_arena *h, double temp, int32_t *actions_dev, int8_t *states_dev, float *tree_probs_dev,
                       double *q_dev, uint8_t *q_f64_dev, uint8_t *recorded_dev, spmcts_stream stream) {
   if (!h) return fail(-1, "null arena");
@@ -1010,6 +1063,20 @@ int spmcts_export_moves(spmcts_arena *h, int8_t *states_dev, float *tree_probs_d
   TRY(launch(k_export, max_records, 256, s, h->v, h->A, h->cells, states_dev, tree_probs_dev, q_dev, q_f64_dev, z_dev,
              game_dev, max_records, count_dev));
   return launch(k_export_clear, 1, 1, s, h->v);
+}
+
+int spmcts_export_games(spmcts_arena *h, int64_t *id_dev, int32_t *slot_dev, int8_t *result_dev, uint8_t *swap_dev,
+                        int32_t *plies_dev, int32_t *opening_dev, uint8_t *moves_dev, int32_t max_records,
+                        int32_t *count_dev, spmcts_stream stream) {
+  if (!h) return fail(-1, "null arena");
+  if (h->log_allocs.empty()) return fail(-4, "the arena has no game log (spmcts_games_set_log)");
+  if (max_records < 0) return fail(-3, "max_records must not be negative");
+  if (max_records > 0 && (!id_dev || !slot_dev || !result_dev || !swap_dev || !plies_dev || !opening_dev || !moves_dev))
+    return fail(-1, "null argument");
+  hipStream_t s = (hipStream_t)stream;
+  TRY(launch(k_export_games, max_records, 256, s, h->v, h->cells, id_dev, slot_dev, result_dev, swap_dev, plies_dev,
+             opening_dev, moves_dev, max_records, count_dev));
+  return launch(k_export_games_clear, 1, 1, s, h->v);
 }
 
 int spmcts_games_state(spmcts_arena *h, uint8_t *active, int32_t *ply, uint8_t *swap, int64_t *game_id) {
@@ -1293,6 +1360,45 @@ int spmcts_valid_moves_host(int32_t game, int32_t width, int32_t height, const i
     using G = decltype(g);
     const uint32_t m = legal_mask<G>(from_cells<G>(board));
     for (int a = 0; a < G::A; ++a) valid[a] = (m >> a) & 1u;
+    return 0;
+  });
+}
+
+// ---- game records ----------------------------------------------------------------
+static int lp_check(int32_t n, int32_t first_ply, int32_t max_rows, const void *const *ptrs, int np) {
+  if (n < 0) return fail(-3, "n must not be negative");
+  if (first_ply < 0) return fail(-3, "first_ply must not be negative");
+  if (max_rows < 0) return fail(-3, "max_rows must not be negative");
+  for (int i = 0; i < np; ++i)
+    if (!ptrs[i] && (n > 0 && (i < 4 || max_rows > 0))) return fail(-1, "null argument");
+  return 0;
+}
+
+int spmcts_log_positions(int32_t game, int32_t width, int32_t height, const uint8_t *moves_dev, const int32_t *plies_dev,
+                         int32_t n, int32_t first_ply, int32_t max_rows, int8_t *boards_dev, int8_t *players_dev,
+                         int32_t *row_record_dev, int32_t *row_ply_dev, uint8_t *status_dev, int32_t *offsets_dev,
+                         spmcts_stream stream) {
+  return with_game(game, width, height, [&](auto g) {
+    using G = decltype(g);
+    const void *ptrs[8] = {moves_dev, plies_dev, status_dev, offsets_dev, boards_dev, players_dev, row_record_dev, row_ply_dev};
+    TRY(lp_check(n, first_ply, max_rows, ptrs, 8));
+    if (n == 0) return 0;
+    const hipStream_t s = (hipStream_t)stream;
+    TRY(launch(k_log_status<G>, n, 128, s, moves_dev, plies_dev, n, first_ply, status_dev, offsets_dev));
+    TRY(launch(k_log_scan, 1024, 1024, s, offsets_dev, n));  // one block
+    return launch(k_log_rows<G>, n, 128, s, moves_dev, plies_dev, n, first_ply, status_dev, offsets_dev, max_rows,
+                  boards_dev, players_dev, row_record_dev, row_ply_dev);
+  });
+}
+
+int spmcts_log_positions_host(int32_t game, int32_t width, int32_t height, const uint8_t *moves, const int32_t *plies,
+                              int32_t n, int32_t first_ply, int32_t max_rows, int8_t *boards, int8_t *players,
+                              int32_t *row_record, int32_t *row_ply, uint8_t *status, int32_t *offsets) {
+  return with_game(game, width, height, [&](auto g) {
+    const void *ptrs[8] = {moves, plies, status, offsets, boards, players, row_record, row_ply};
+    TRY(lp_check(n, first_ply, max_rows, ptrs, 8));
+    if (n == 0) return 0;
+    lp_host<decltype(g)>(moves, plies, n, first_ply, max_rows, boards, players, row_record, row_ply, status, offsets);
     return 0;
   });
 }

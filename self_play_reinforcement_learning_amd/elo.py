@@ -12,7 +12,8 @@ Departures from the reference, both deliberate:
 
 * The database is a directory of plain files instead of three shelves of pickles: `models.json` (name -> policy
   class name, JSON-able policy kwargs, net shape), `weights/<name>.pt` (the network's state_dict, read with
-  weights_only=True), `results.json` and `elo.json`.  Nothing in it is executable.
+  weights_only=True), `results.json` and `elo.json`; with game records also `games/<key>.json` (the move lists
+  of a pairing's games, records.GameRecords) and `accuracy.json` (Elo.grade).  Nothing in it is executable.
 * `calculate_elo` fits the reference's model (elo.py:176-191: expected score q1 / (q1 + q2), q = 10^(r / 400),
   binary cross-entropy against 1 / 0.5 / 0, the anchor fixed) but solves it as a deterministic full-batch
   maximum-likelihood fit (damped Newton in float64, to a gradient norm below GRAD_TOL) where the reference runs
@@ -25,6 +26,12 @@ Command line (the two rating commands of the reference's main.py):
 
     python -m self_play_reinforcement_learning_amd.elo compare_models --dir D --g connect4 [--b W H] [--p names...]
     python -m self_play_reinforcement_learning_amd.elo calculate_elo --dir D --g connect4 [--b W H]
+
+and, on the game records the arenas leave behind (records.py):
+
+    ... elo compare_models --record ...       also keep every game's moves in D/games/<key>.json
+    ... elo grade --dir D [--p names...]      the stored games' endgame moves against the exact solver -> accuracy.json
+    ... elo observe --dir D --p a b           the reference's main.py observe: one game per colour, printed ply by ply
 """
 import itertools
 import json
@@ -75,6 +82,8 @@ class ModelDatabase:
         self._models = os.path.join(self.directory, "models.json")
         self._results = os.path.join(self.directory, "results.json")
         self._elo = os.path.join(self.directory, "elo.json")
+        self._accuracy = os.path.join(self.directory, "accuracy.json")
+        self._games = os.path.join(self.directory, "games")
 
     # ------------------------------------------------------------------ models
     def models(self):
@@ -150,6 +159,33 @@ class ModelDatabase:
 
     def set_elos(self, ratings):
         _write_json(self._elo, {"elo": ratings})
+
+    # ------------------------------------------------------------------ game records and their grading
+    def game_keys(self):
+        """The result keys ("a__b") that have stored game records (games/<key>.json), sorted."""
+        if not os.path.isdir(self._games):
+            return []
+        return sorted(f[:-5] for f in os.listdir(self._games) if f.endswith(".json"))
+
+    def games(self, key):
+        """The stored records of a result key (records.GameRecords; None if there are none)."""
+        from .records import GameRecords
+
+        path = os.path.join(self._games, f"{key}.json")
+        return GameRecords.load(path) if os.path.exists(path) else None
+
+    def add_games(self, key, records):
+        """Append records to games/<key>.json (JSON, data only)."""
+        os.makedirs(self._games, exist_ok=True)
+        old = self.games(key)
+        _write_json(os.path.join(self._games, f"{key}.json"), (old.extend(records) if old else records).to_json())
+
+    def accuracy(self):
+        """name -> {"graded", "strong", "weak", "blunders"} once Elo.grade has run, else {}."""
+        return _read_json(self._accuracy, {})
+
+    def set_accuracy(self, accuracy):
+        _write_json(self._accuracy, accuracy)
 
 
 def result_key(model_1, model_2):
@@ -278,13 +314,19 @@ class Elo:
                 out.append(dict(kind="random" if e["policy"] == "Random" else "lookahead"))
         return out
 
-    def compare_models(self, *names, num_games=100, openings=None):
+    def named_players(self, names):
+        """players(names) with each dict's "name" set: the names a league's game records carry."""
+        return [dict(p, name=n) for p, n in zip(self.players(names), names)]
+
+    def compare_models(self, *names, num_games=100, openings=None, record_games=False):
         """Play num_games games (rounded up to an even number) between every two of `names`, all C(n, 2)
         pairings in one league arena, and add the results to results.json under the reference's keys
         (elo.py:45-71).  Returns the new results per key.  openings: an opening book (a list of move lists, or
         openings.parse_openings' forms "all:N" / a JSON file): each pairing's games 2k and 2k + 1 start from
         opening k mod len(openings), once per colour; None = every game starts on the empty board.  The counts
-        keep their keys and meaning either way."""
+        keep their keys and meaning either way.  record_games: also keep every game's move list (the arena's game
+        log): each pairing's records are appended to games/<key>.json in the database directory, <key> the pairing's
+        results.json key; the records carry both players' names, so they need no turning round."""
         from .arena import game_of_env
         from .engine import LeagueEngine
         from .openings import parse_openings
@@ -297,15 +339,75 @@ class Elo:
             raise ValueError("compare_models needs at least two different models")
         pairings = list(itertools.combinations(range(len(names)), 2))
         game = game_of_env(self.model_database.env)
-        eng = LeagueEngine(game, self.players(names), pairings, games_per_pairing=num_games,
+        eng = LeagueEngine(game, self.named_players(names), pairings, games_per_pairing=num_games,
                            seed=self.seed + 7919 * self.calls, search_threads=self.search_threads, dtype=self.dtype,
-                           device=self.device, openings=parse_openings(openings, game))
+                           device=self.device, openings=parse_openings(openings, game), record_games=record_games)
         self.calls += 1
         try:
             breakdowns = eng.play()
+            if record_games:
+                self.store_games(names, pairings, eng.game_records())
         finally:
             eng.close()
         return self.accumulate([(names[i], names[j]) for i, j in pairings], breakdowns)
+
+    def store_games(self, names, pairings, records):
+        """Each pairing's records (a league's GameRecords, split by their pairing) into games/<key>.json."""
+        from .records import GameRecords
+
+        for p, (i, j) in enumerate(pairings):
+            part = GameRecords(records.game)
+            sel = np.flatnonzero(records.pairing == p)
+            part.append_arrays(*[getattr(records, k)[sel] for k in GameRecords._ARRAYS],
+                               names=[records.names[r] for r in sel])
+            self.model_database.add_games(result_key(names[i], names[j])[0], part)
+
+    def grade(self, *names, max_empty=12, device=None):
+        """Grade the stored game records against the exact solver (records.grade_games: the positions with at most
+        max_empty empty cells): per model the endgame moves graded, those that were best (strong), those that kept
+        the game's exact outcome (weak) and the blunders.  names: the models whose games count (default: every
+        stored pairing); a pairing is read only if both its models are named.  Written to accuracy.json next to
+        elo.json and returned."""
+        from .arena import game_of_env
+        from .records import grade_games
+
+        db = self.model_database
+        game = game_of_env(db.env)
+        out = {}
+        for key in db.game_keys():
+            records = db.games(key)
+            if names and not {n for pair in records.names if pair for n in pair} <= set(names):
+                continue
+            g = grade_games(game, records, max_empty=max_empty, device=device if device is not None else self.device)
+            for name, c in g["players"].items():
+                acc = out.setdefault(name, dict(graded=0, strong=0, weak=0, blunders=0))
+                for k in acc:
+                    acc[k] += int(c[k])
+        db.set_accuracy(out)
+        return out
+
+    def observe(self, name_1, name_2, openings=None, out=print):
+        """The reference's main.py observe (ModelDatabase.observe with View): the two models play one game per
+        colour in a league arena with the game log on, and each game is printed ply by ply
+        (records.GameRecords.render).  Nothing is stored.  Returns the records."""
+        from .arena import game_of_env
+        from .engine import LeagueEngine
+        from .openings import parse_openings
+
+        game = game_of_env(self.model_database.env)
+        eng = LeagueEngine(game, self.named_players([name_1, name_2]), [(0, 1)], games_per_pairing=2,
+                           seed=self.seed + 7919 * self.calls, search_threads=self.search_threads, dtype=self.dtype,
+                           device=self.device, openings=parse_openings(openings, game), record_games=True)
+        self.calls += 1
+        try:
+            eng.play()
+            records = eng.game_records()
+        finally:
+            eng.close()
+        for i in np.argsort(records.ids, kind="stable"):
+            out(records.render(int(i)))
+            out("")
+        return records
 
     def accumulate(self, pairs, breakdowns):
         """Add each pairing's breakdown ({"first": {...}, "second": {...}} in the first model's view) to
@@ -340,7 +442,7 @@ def main(argv=None):
     from .envs import Connect4Env, TicTacToeEnv
 
     parser = argparse.ArgumentParser(description="rate registered models (the reference's main.py commands)")
-    parser.add_argument("command", choices=["compare_models", "calculate_elo"])
+    parser.add_argument("command", choices=["compare_models", "calculate_elo", "grade", "observe"])
     parser.add_argument("--dir", required=True, help="the ModelDatabase directory")
     parser.add_argument("--g", dest="game", default="connect4", choices=["connect4", "tictactoe"])
     parser.add_argument("--b", nargs="*", dest="board_size", help="board size: W H")
@@ -349,15 +451,25 @@ def main(argv=None):
     parser.add_argument("--openings", default=None,
                         help="opening book: all:N (every N-ply opening) or a JSON file "
                              "of move lists; each opening is played once per colour in every pairing")
+    parser.add_argument("--record", action="store_true",
+                        help="compare_models: keep every game's moves in <dir>/games/<key>.json")
+    parser.add_argument("--max-empty", type=int, default=12,
+                        help="grade: the exact solver takes the positions with at most this many empty cells")
     args = parser.parse_args(argv)
     env = {"connect4": Connect4Env, "tictactoe": TicTacToeEnv}[args.game](*[int(x) for x in args.board_size or []])
     elo = Elo(ModelDatabase(args.dir, env))
     if args.command == "calculate_elo":
         print(json.dumps(elo.calculate_elo(), indent=1, sort_keys=True))
-    elif args.p:
-        print(json.dumps(elo.compare_models(*args.p, num_games=args.games, openings=args.openings), indent=1, sort_keys=True))
+    elif args.command == "grade":
+        print(json.dumps(elo.grade(*(args.p or []), max_empty=args.max_empty), indent=1, sort_keys=True))
+    elif args.command == "observe":
+        if not args.p or len(args.p) != 2:
+            parser.error("observe needs --p with two model names")
+        elo.observe(*args.p, openings=args.openings)
     else:
-        print(json.dumps(elo.compare_all(num_games=args.games, openings=args.openings), indent=1, sort_keys=True))
+        names = args.p or list(elo.model_database.models().keys())
+        print(json.dumps(elo.compare_models(*names, num_games=args.games, openings=args.openings,
+                                            record_games=args.record), indent=1, sort_keys=True))
 
 
 if __name__ == "__main__":

@@ -102,8 +102,10 @@ class SelfPlayEngine:
                  leaf_layout="nhwc", cpuct=4.0, x_noise=0.25, blocks_per_tree=0, bucket=256, opponent=None,
                  opponent_iterations=None, record=True, search_threads=1, leaf_dedup=None, opponent_alpha=None,
                  opponent_strong_play=None, opponent_search_threads=None, eval_cache=None, openings=None,
-                 opening_period=0, opponent_depth=2):
-        """opponent_depth: the horizon of opponent="negamax" (hardcoded_players.Negamax; 1 .. 6 on the device).
+                 opening_period=0, opponent_depth=2, record_games=False):
+        """record_games: keep every finished game's move list (the arena's game log, include/spmcts.h
+        spmcts_games_set_log; drained once per ply next to the Move export): game_records() returns them.
+        opponent_depth: the horizon of opponent="negamax" (hardcoded_players.Negamax; 1 .. 6 on the device).
         openings: an opening book, a list of move lists from the empty board (openings.py; include/spmcts.h
         spmcts_games_set_openings): game id i starts from opening ((i mod opening_period) >> 1) mod len(openings),
         its book plies played without a search; None = every game starts on the empty board.
@@ -187,6 +189,9 @@ class SelfPlayEngine:
         if openings:
             self.openings = validate_openings(game, openings)
             self.arena.games_set_openings(self.openings, int(opening_period))
+        self.record_games, self._records = False, None
+        if record_games:
+            self.enable_game_records()
         self.n_games = n_games
         self.max_games = max_games
         # torch convolutions want few distinct shapes; the fused HIP tower takes any batch
@@ -391,10 +396,28 @@ class SelfPlayEngine:
             exported = int(moves["z"].shape[0])
             if on_moves is not None:
                 on_moves(moves)
+        if self.record_games:  # the ply's finished games (drained with the Move export), ids offset like the Move rows'
+            self._records.append_export(self.arena.last_games, id_offset=game_offset)
         self.games_done += finished
         self.positions += exported
         self.plies += 1
         return finished, exported
+
+    def enable_game_records(self):
+        """What record_games=True does, for an engine that exists already: the arena's game log on (while no game is
+        active: before start(), or between play_games() calls that ran to their end)."""
+        from .records import GameRecords
+
+        self.arena.games_set_log(True)
+        self.record_games = True
+        if self._records is None:
+            self._records = GameRecords(self.game)
+
+    def game_records(self):
+        """The records of the games finished so far (records.GameRecords; record_games=True)."""
+        if not self.record_games:
+            raise ValueError("the engine was built without record_games=True")
+        return self._records
 
     def _device_count_ok(self):
         return self.async_device and all(getattr(ev, "supports_device_count", False)
@@ -800,6 +823,16 @@ class LanedEngine:
     def weights_snapshot(self):
         return all(e.weights_snapshot for e in self.lanes)
 
+    def game_records(self):
+        """The union of the lanes' game records (record_games=True), lane i's ids offset by i * 2**40 like its
+        Move rows."""
+        from .records import GameRecords
+
+        out = GameRecords(self.lanes[0].game)
+        for e in self.lanes:
+            out.extend(e.game_records())
+        return out
+
     def counters(self):
         cs = self._each(lambda e: e.counters())
         out = {}
@@ -851,8 +884,10 @@ class LeagueEngine:
 
     def __init__(self, game, players, pairings, games_per_pairing=100, seed=0, search_threads=4,
                  dtype=torch.float16, subsequence0=0, device=None, leaf_layout="nhwc", cpuct=4.0, x_noise=0.25,
-                 blocks_per_tree=0, openings=None, rng="philox"):
-        """rng: "philox", or "tape" (every tree draws from its own given stream: Arena.set_tapes before start()).
+                 blocks_per_tree=0, openings=None, rng="philox", record_games=False):
+        """record_games: keep every game's move list (the arena's game log, drained once per ply); game_records()
+        returns them with each record's pairing and its two players' names (a player dict's "name", else its index).
+        rng: "philox", or "tape" (every tree draws from its own given stream: Arena.set_tapes before start()).
         openings: an opening book (openings.py) with id period g, the per-pairing slot count: every pairing
         walks the suite from its first opening, slots 2k and 2k + 1 of a pairing play opening k mod len(openings)
         once per colour.  None = every game starts on the empty board."""
@@ -920,6 +955,13 @@ class LeagueEngine:
                           search_threads=[min(a.search_threads, max(1, int(x))) for x in per_tree("search_threads", K0)])
         a.set_tree_players(nets=None, kinds=kinds, budgets=[int(x) for x in per_tree("iterations", 100)])
         a.games_set_record(False)
+        self.record_games = bool(record_games)
+        self._records = None
+        if self.record_games:
+            from .records import GameRecords
+
+            a.games_set_log(True)
+            self._records = GameRecords(game)
         self.n_nets = len(self.evaluators)
         if self.n_nets:
             a.set_league(tree_net, self.n_nets)
@@ -1002,9 +1044,21 @@ class LeagueEngine:
         a.games_end_ply_async()
         self._eval_expand()
         finished, _ = a.games_finish_ply(refill=False)
+        if self.record_games:
+            ex = a.export_games()
+            pairing = (ex["slot"] // self.g).cpu().numpy()  # slot s belongs to pairing s // g (league_schedule)
+            names = [[str(self.players[k].get("name", k)) for k in self.schedule[p][1:]] for p in pairing]
+            self._records.append_export(ex, pairing=pairing.astype("int32"), names=names)
         self.games_done += finished
         self.plies += 1
         return finished
+
+    def game_records(self):
+        """The records of the games finished so far (records.GameRecords; record_games=True): side 0 is the
+        pairing's first player, side 1 its second."""
+        if not self.record_games:
+            raise ValueError("the engine was built without record_games=True")
+        return self._records
 
     def play(self):
         """Play every slot's game to its end.  Returns, per pairing, {"first": {wins, draws, losses}, "second":

@@ -432,13 +432,16 @@ class SelfPlayScheduler:
                               seed=self.seed + 104729 + 7919 * self.rank, device=self.device, opponent=opponent,
                               record=False, search_threads=self._search_threads, openings=openings, **opp_kw), per_rank
 
-    def _play_evaluation(self, n_games, openings=None):
+    def _play_evaluation(self, n_games, openings=None, records=None):
         """n_games evaluation games over all ranks (task i -> swap_sides = i odd, update=False);
         returns the reference's result dicts (self_play_parallel.py:294-300, :366-371).  openings: an opening
-        book (each rank's game i starts from opening (i >> 1) mod len(openings))."""
+        book (each rank's game i starts from opening (i >> 1) mod len(openings)).  records: a list that receives
+        the engine's GameRecords (single process)."""
         if n_games <= 0:
             return []
         eng, per_rank = self._evaluation_engine(n_games, openings)
+        if records is not None:
+            eng.enable_game_records()
         c0 = eng.counters()["results"]
         eng.play_games(per_rank)
         eng.check()
@@ -449,6 +452,8 @@ class SelfPlayScheduler:
         for s in range(2):
             for k, r in enumerate((1, 0, -1)):
                 reward_list += [{"reward": r, "swap_sides": bool(s)}] * flat[3 * s + k]
+        if records is not None:
+            records.append(eng.game_records())
         eng.arena.close()
         return reward_list
 
@@ -497,17 +502,21 @@ class SelfPlayScheduler:
         return total
 
     def compare_models(self, num_workers=None, inference_proxy=True, threads_per_worker=8, resume_model=False,
-                       gpus=None, openings=None):
+                       gpus=None, openings=None, record_games=False):
         """self_play_parallel.py:355-379: epoch_length evaluation games, policy network vs the
         evaluation policy (a second network on the same arena, or a hard-coded player).
         Returns (total_rewards, breakdown) exactly as the reference's parse_results; with gpus > 1
         the games are sharded over one rank process per GPU.  openings: an opening book (openings.py: a list of
         move lists, "all:N", or a JSON file); games 2k and 2k + 1 start from opening k mod len(openings), once
-        per colour; None = every game starts on the empty board."""
+        per colour; None = every game starts on the empty board.  record_games: also return the games' move lists
+        (records.GameRecords: side 0 the policy, side 1 the evaluation policy) as a third element; one process
+        only."""
         from .openings import parse_openings
 
         openings = parse_openings(openings, self.game)
         n = self._ranks(gpus)
+        if record_games and (n > 1 or self.world > 1):
+            raise ValueError("record_games=True needs a single process (gpus=1)")
         if n > 1:
             return self._run_ranks(n, "compare_models", dict(num_workers=num_workers, inference_proxy=inference_proxy,
                                                               threads_per_worker=threads_per_worker,
@@ -515,7 +524,12 @@ class SelfPlayScheduler:
         if resume_model:
             self._load_latest(prev_run=True)
         self._resolve_threads(inference_proxy)  # evaluation workers talk to the InferenceProxy too
-        reward_list = self._play_evaluation(self.epoch_length, openings)
+        records = [] if record_games else None
+        reward_list = self._play_evaluation(self.epoch_length, openings, records)
+        if record_games:
+            from .records import GameRecords
+
+            return (*self.parse_results(reward_list), records[0] if records else GameRecords(self.game))
         return self.parse_results(reward_list)
 
 
