@@ -271,6 +271,40 @@ int spmcts_root_stats_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n
                             double *child_w_dev, float *child_p_dev, int32_t *root_n_dev, double *root_w_dev,
                             int8_t *root_player_dev, int8_t *boards_dev, spmcts_stream stream);
 
+/* ---- reading the trees below the root (read-only; csrc/arena_tree.h) ------- */
+/* The principal variation of each of the n listed trees, queued on the stream with no host synchronisation: from
+ * the active root, the child with the largest n (the lowest action on ties: ns.index(max(ns)), mcts.py:290-295),
+ * while that n is at least max(min_visits, 1), the node has a child block, the game goes on and fewer than
+ * max_len (1 .. W*H) moves are out.  Per tree i: pv int8 [n][max_len] (-1 past the end); pv_n, pv_vl int32, pv_w
+ * double, pv_p float [n][max_len], the chosen children's fields as stored (entries past the end are not written;
+ * vl is 0 in an arena with search_threads 1, which keeps no virtual loss); pv_len int32 [n]; pv_end uint8 [n]
+ * (0: cut at max_len, 1: the last node has no child with enough visits, 2: the last move ended the game);
+ * end_board int8 [n][W*H], the board after the last move (tree frame, cells as spmcts_root_stats_batch).  Any
+ * output may be NULL.  A tree id outside the arena raises SPMCTS_ERR_STATE and leaves its row untouched.
+ * -1: null handle; -3: n < 0, max_len outside [1, W*H], min_visits < 0; n == 0 launches nothing. */
+int spmcts_tree_pv_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n, int32_t max_len, int32_t min_visits,
+                         int8_t *pv_dev, int32_t *pv_n_dev, int32_t *pv_vl_dev, double *pv_w_dev, float *pv_p_dev,
+                         int32_t *pv_len_dev, uint8_t *pv_end_dev, int8_t *end_board_dev, spmcts_stream stream);
+/* Bytes of the work buffer spmcts_tree_export_batch needs for n trees of max_nodes entries (24 per queue slot: the
+ * queued node's two board masks and its child block and depth; plus 8 * (W*H + 1) per tree for the counting walk). */
+int spmcts_tree_export_work_bytes(spmcts_arena *h, int32_t n, int32_t max_nodes, uint64_t *bytes_out);
+/* The subtree under the active root of each of the n listed trees in breadth-first order, no host synchronisation.
+ * Entry 0 is the root; for entry e in order, its children with n >= min_visits (0: every child of every expanded
+ * node, invalid ones included) whose depth is within max_depth (< 0: no limit) follow in ascending action order.
+ * Per tree, [n][max_nodes] each: parent int32 (index in the row, -1 for the root), action int8 (-1 for the root),
+ * depth int16, node_n / node_vl int32, node_w double, node_p float (as stored; vl as in spmcts_tree_pv_batch),
+ * player int8 (root player * (-1)^depth: MCNode.player), flags uint8 (bit 0: expanded, bit 1: valid, set for the
+ * root, bit 2: the move into the node ended the game).  count int32 [n]: the nodes that qualify; where it exceeds
+ * max_nodes exactly the first max_nodes are written and nothing past them is touched (not an error: call again
+ * with more room).  Any output may be NULL.  work_dev: device scratch of spmcts_tree_export_work_bytes bytes,
+ * 8-byte aligned, no initial contents needed.  A tree id outside the arena raises SPMCTS_ERR_STATE and leaves
+ * its row untouched.  -1: null handle / trees / work; -3: n < 0, max_nodes < 1, min_visits < 0, work too small. */
+int spmcts_tree_export_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n, int32_t max_nodes,
+                             int32_t min_visits, int32_t max_depth, int32_t *parent_dev, int8_t *action_dev,
+                             int16_t *depth_dev, int32_t *node_n_dev, int32_t *node_vl_dev, double *node_w_dev,
+                             float *node_p_dev, int8_t *player_dev, uint8_t *flags_dev, int32_t *count_dev,
+                             void *work_dev, uint64_t work_bytes, spmcts_stream stream);
+
 /* ---- games-level API (SelfPlayer.play_episode state machine) -------------- */
 /* Start games in the listed slots (selfplayworker.py:172-179): both trees reset,
  * swap_sides = game id odd (self_play_parallel.py:237).  Game ids continue from

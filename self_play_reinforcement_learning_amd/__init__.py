@@ -16,7 +16,9 @@ has no form of: opening books (openings.py: enumerate_openings, validate_opening
 exact depth-limited solver (solve_positions, tactical_report), and the exact solver to the end of the game
 (solve.py: SolveTable, solve_to_end, perfect_report) with the reference's PerfectEvaluator
 (games/algos/evaluation_worker.py) on top of it, and game records (records.py: GameRecords, the move lists the
-arenas' games leave behind with record_games=True; grade_games, their moves held against the exact solvers).
+arenas' games leave behind with record_games=True; grade_games, their moves held against the exact solvers), and
+the search trees below the root (tree.py: TreeView over Arena.export_subtrees; Arena.pv_batch,
+MCTreeSearch.principal_variation / .tree).
 """
 from .base_model import BasePlayer, ModelContainer, Policy, TrainableModel  # noqa: F401
 from .memory import Memory  # noqa: F401
@@ -42,6 +44,7 @@ _LAZY = {
     "PerfectEvaluator": ".evaluation_worker",
     "GameRecords": ".records",
     "grade_games": ".records",
+    "TreeView": ".tree",
     "enumerate_openings": ".openings",
     "validate_openings": ".openings",
     "SelfPlayScheduler": ".self_play_parallel",

@@ -125,6 +125,9 @@ _SIGS = {
     "spmcts_openings_validate": [_I32, _I32, _I32, _P, _P, _I32, _I32],
     "spmcts_games_openings": [_P, _P],
     "spmcts_root_stats_batch": [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
+    "spmcts_tree_pv_batch": [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "spmcts_tree_export_work_bytes": [_P, _I32, _I32, ctypes.POINTER(_U64)],
+    "spmcts_tree_export_batch": [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P],
     "spmcts_set_league": [_P, _P, _I32],
     "spmcts_league_segments": [_P, _P],
     "spmcts_league_route": [_P, _P, _P, _I32, _P, _P, _P],

@@ -398,6 +398,67 @@ class Arena:
         self._stats_trees = t  # alive until the kernel has run
         return out
 
+    def pv_batch(self, trees, max_len=None, min_visits=1):
+        """The principal variation of the listed trees (a list or a device int32 tensor) as device tensors, queued
+        on the current stream without a host synchronisation (include/spmcts.h spmcts_tree_pv_batch): from the
+        active root the most visited child, the lowest action on ties, while it has at least max(min_visits, 1)
+        visits, for at most max_len moves (default: the board's cells).  pv int8 [n, max_len] (-1 past the end),
+        pv_n / pv_vl int32, pv_w float64, pv_p float32 [n, max_len] (the chosen children's fields, 0 past the end),
+        pv_len int32 [n], pv_end uint8 [n] (0 cut at max_len, 1 no child with enough visits, 2 the game ended),
+        end_board int8 [n, W, H] (tree frame)."""
+        t = trees.to(self.device, torch.int32).contiguous() if torch.is_tensor(trees) else self._dev_i32(trees)
+        n, dev = int(t.numel()), self.device
+        L = self.cells if max_len is None else int(max_len)
+        out = dict(pv=torch.full((n, L), -1, dtype=torch.int8, device=dev),
+                   pv_n=torch.zeros((n, L), dtype=torch.int32, device=dev),
+                   pv_vl=torch.zeros((n, L), dtype=torch.int32, device=dev),
+                   pv_w=torch.zeros((n, L), dtype=torch.float64, device=dev),
+                   pv_p=torch.zeros((n, L), dtype=torch.float32, device=dev),
+                   pv_len=torch.zeros(n, dtype=torch.int32, device=dev),
+                   pv_end=torch.zeros(n, dtype=torch.uint8, device=dev),
+                   end_board=torch.zeros((n, self.W, self.H), dtype=torch.int8, device=dev))
+        call("spmcts_tree_pv_batch", self.h, ptr(t), n, L, int(min_visits), ptr(out["pv"]), ptr(out["pv_n"]),
+             ptr(out["pv_vl"]), ptr(out["pv_w"]), ptr(out["pv_p"]), ptr(out["pv_len"]), ptr(out["pv_end"]),
+             ptr(out["end_board"]), _stream())
+        self._pv_trees = t  # alive until the kernel has run
+        return out
+
+    EXPORT_FIELDS = (("parent", torch.int32, -1), ("action", torch.int8, -1), ("depth", torch.int16, 0),
+                     ("node_n", torch.int32, 0), ("node_vl", torch.int32, 0), ("node_w", torch.float64, 0),
+                     ("node_p", torch.float32, 0), ("player", torch.int8, 0), ("flags", torch.uint8, 0))
+
+    def export_subtrees(self, trees, max_nodes, min_visits=1, max_depth=None, out=None):
+        """The subtree under the active root of the listed trees in breadth-first order as device tensors, queued
+        on the current stream without a host synchronisation (include/spmcts.h spmcts_tree_export_batch).  Row i
+        lists tree trees[i]: entry 0 the root, then for each entry in order its children with at least min_visits
+        visits (0: every child of every expanded node) at a depth of at most max_depth (None: no limit), in action
+        order.  [n, max_nodes] each, padded: parent int32 (-1 for the root and the padding), action int8 (-1
+        likewise), depth int16, node_n / node_vl int32, node_w float64, node_p float32, player int8, flags uint8
+        (bit 0 expanded, bit 1 valid, bit 2 terminal); count int32 [n], the nodes that qualify: where it exceeds
+        max_nodes the first max_nodes are there and the call may be repeated with more room (tree.TreeView's
+        `truncated`).  out: a dict of the caller's own contiguous device tensors to write into instead of new ones
+        (the same keys and dtypes; rows of max_nodes entries from the start of each, so at least n * max_nodes
+        elements; whatever lies past them is not touched)."""
+        t = trees.to(self.device, torch.int32).contiguous() if torch.is_tensor(trees) else self._dev_i32(trees)
+        n, M, dev = int(t.numel()), int(max_nodes), self.device
+        if out is None:
+            out = {k: torch.full((n, M), fill, dtype=dt, device=dev) for k, dt, fill in self.EXPORT_FIELDS}
+            out["count"] = torch.zeros(n, dtype=torch.int32, device=dev)
+        else:
+            for k, dt, _ in self.EXPORT_FIELDS + (("count", torch.int32, 0),):
+                need = n if k == "count" else n * max(M, 0)
+                if out[k].dtype != dt or out[k].device != dev or not out[k].is_contiguous() or out[k].numel() < need:
+                    raise ValueError(f"export_subtrees: out[{k!r}] must be a contiguous {dt} tensor on {dev} with at "
+                                     f"least {need} elements")
+        nbytes = ctypes.c_uint64()
+        call("spmcts_tree_export_work_bytes", self.h, n, M, ctypes.byref(nbytes))
+        work = torch.empty((nbytes.value + 7) // 8, dtype=torch.int64, device=dev)
+        depth = -1 if max_depth is None else int(max_depth)
+        call("spmcts_tree_export_batch", self.h, ptr(t), n, M, int(min_visits), depth,
+             *[ptr(out[k]) for k, _, _ in self.EXPORT_FIELDS], ptr(out["count"]), ptr(work), nbytes.value, _stream())
+        self._export_keep = (t, work)  # alive until the kernel has run
+        return out
+
     # ------------------------------------------------------------------ games API
     def games_set_openings(self, openings, id_period=0):
         """The arena's opening book (include/spmcts.h spmcts_games_set_openings): `openings` a list of move

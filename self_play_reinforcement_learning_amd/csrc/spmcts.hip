@@ -34,6 +34,7 @@
 //   negamax.h       exact depth-limited negamax: the search core (host and device), its batch and arena kernels
 //   solve.h         exact solver to the end of the game: alpha-beta with a transposition table, resumable launches
 //   arena_games.h   game state machine (opening book plies included), the hard-coded players, k_root_stats_batch, export
+//   arena_tree.h    reading the trees below the root: k_tree_pv (principal variations), k_tree_export (subtrees)
 //   records.h       game records (move lists) to the positions before their moves: spmcts_log_positions and its host twin
 //   arena_misc.h    k_env_step, k_table_net, k_copy_probe, the init kernels
 //   arena_league.h  league routing: a step's rows partitioned by their tree's network, and back
@@ -93,6 +94,7 @@ static int fail(int code, const std::string &msg) {
 #include "negamax.h"
 #include "solve.h"
 #include "arena_games.h"
+#include "arena_tree.h"
 #include "records.h"
 #include "arena_misc.h"
 #include "arena_league.h"
@@ -1183,6 +1185,51 @@ int spmcts_root_stats_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n
   if (!trees_dev) return fail(-1, "null argument");
   return LAUNCH(h, k_root_stats_batch, (long long)n * h->P, 256, (hipStream_t)stream, h->v, trees_dev, n, child_n_dev,
                 child_w_dev, child_p_dev, root_n_dev, root_w_dev, root_player_dev, boards_dev);
+}
+
+// ---- reading the trees ------------------------------------------------------
+int spmcts_tree_pv_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n, int32_t max_len, int32_t min_visits,
+                         int8_t *pv_dev, int32_t *pv_n_dev, int32_t *pv_vl_dev, double *pv_w_dev, float *pv_p_dev,
+                         int32_t *pv_len_dev, uint8_t *pv_end_dev, int8_t *end_board_dev, spmcts_stream stream) {
+  if (!h) return fail(-1, "null arena");
+  if (n < 0) return fail(-3, "tree_pv: n must not be negative");
+  if (max_len < 1 || max_len > h->cells) return fail(-3, "tree_pv: max_len must be in [1, width * height]");
+  if (min_visits < 0) return fail(-3, "tree_pv: min_visits must not be negative");
+  if (n == 0) return 0;
+  if (!trees_dev) return fail(-1, "null argument");
+  const TreePvOut o{pv_dev, pv_n_dev, pv_vl_dev, pv_w_dev, pv_p_dev, pv_len_dev, pv_end_dev, end_board_dev};
+  return LAUNCH(h, k_tree_pv, (long long)n * h->P, 256, (hipStream_t)stream, h->v, trees_dev, n, max_len, min_visits,
+                o);
+}
+
+int spmcts_tree_export_work_bytes(spmcts_arena *h, int32_t n, int32_t max_nodes, uint64_t *bytes_out) {
+  if (!h || !bytes_out) return fail(-1, "null argument");
+  if (n < 0 || max_nodes < 1) return fail(-3, "tree_export: n must not be negative and max_nodes at least 1");
+  return with_game(h->cfg.game, h->W, h->H, [&](auto g) {
+    *bytes_out = 8 * (uint64_t)tree_export_work_words<decltype(g)>((size_t)n, (size_t)max_nodes);
+    return 0;
+  });
+}
+
+int spmcts_tree_export_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n, int32_t max_nodes,
+                             int32_t min_visits, int32_t max_depth, int32_t *parent_dev, int8_t *action_dev,
+                             int16_t *depth_dev, int32_t *node_n_dev, int32_t *node_vl_dev, double *node_w_dev,
+                             float *node_p_dev, int8_t *player_dev, uint8_t *flags_dev, int32_t *count_dev,
+                             void *work_dev, uint64_t work_bytes, spmcts_stream stream) {
+  if (!h) return fail(-1, "null arena");
+  if (n < 0) return fail(-3, "tree_export: n must not be negative");
+  if (max_nodes < 1) return fail(-3, "tree_export: max_nodes must be at least 1");
+  if (min_visits < 0) return fail(-3, "tree_export: min_visits must not be negative");
+  if (n == 0) return 0;
+  uint64_t need = 0;
+  TRY(spmcts_tree_export_work_bytes(h, n, max_nodes, &need));
+  if (!trees_dev || !work_dev) return fail(-1, "null argument");
+  if (work_bytes < need || ((uintptr_t)work_dev & 7))
+    return fail(-3, "tree_export: work buffer too small or not 8-byte aligned (spmcts_tree_export_work_bytes)");
+  const TreeExportOut o{parent_dev, action_dev, depth_dev, node_n_dev, node_vl_dev, node_w_dev, node_p_dev, player_dev,
+                        flags_dev, count_dev};
+  return LAUNCH(h, k_tree_export, (long long)n * h->P, 256, (hipStream_t)stream, h->v, trees_dev, n, max_nodes,
+                min_visits, max_depth, o, (uint64_t *)work_dev);
 }
 
 // ---- league ---------------------------------------------------------------

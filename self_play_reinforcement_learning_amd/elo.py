@@ -32,6 +32,10 @@ and, on the game records the arenas leave behind (records.py):
     ... elo compare_models --record ...       also keep every game's moves in D/games/<key>.json
     ... elo grade --dir D [--p names...]      the stored games' endgame moves against the exact solver -> accuracy.json
     ... elo observe --dir D --p a b           the reference's main.py observe: one game per colour, printed ply by ply
+
+and, on one model's search of one position (mcts.analyse_positions with its principal variation and tree):
+
+    ... elo analyse --dir D --p name --moves 3 3 2 [--pv 8] [--tree-depth 2] [--min-visits 2]
 """
 import itertools
 import json
@@ -409,6 +413,48 @@ class Elo:
             out("")
         return records
 
+    def analyse(self, name, moves, pv_len=8, tree_depth=2, min_visits=2, out=None):
+        """One registered MCTreeSearch model's search of the position after `moves` (a move list from the empty
+        board): mcts.analyse_positions with the model's own iterations / alpha / strong_play, its principal
+        variation of at most pv_len moves and its tree to tree_depth (nodes with at least min_visits visits).
+        Returns analyse_positions' dict for the one position plus "view" (the tree.TreeView) and "text" (the root
+        table, the PV and the rendered tree); out (e.g. print) receives the text."""
+        from .arena import game_of_env
+        from .mcts import analyse_positions
+        from .tree import TreeView
+
+        entry = self.model_database.models()[name]
+        if entry["policy"] != "MCTreeSearch":
+            raise ValueError(f"{name!r} is a {entry['policy']} player: only an MCTreeSearch model has a search tree")
+        kw = entry["policy_kwargs"]
+        its = int(kw.get("iterations", 100))
+        game = game_of_env(self.model_database.env)
+        res = analyse_positions(game, self.model_database.network(name), [list(moves)], its,
+                                search_threads=self.search_threads, seed=self.seed, alpha=float(kw.get("alpha", 1)),
+                                strong_play=bool(kw.get("strong_play", False)), device=self.device, dtype=self.dtype,
+                                pv_len=int(pv_len), tree=dict(max_nodes=2 + its, min_visits=int(min_visits),
+                                                              max_depth=tree_depth))
+        view = TreeView.from_export(res["tree"], 0)
+        cn, cw, cp = (res[k][0].cpu().numpy() for k in ("child_n", "child_w", "child_p"))
+        lines = [f"{name}: {its} simulations after moves {list(moves)}; root n={int(res['root_n'][0])} "
+                 f"q={float(res['root_q'][0]):+.3f}, player {int(res['root_player'][0])} to move",
+                 "action      n        q      p"]
+        for a in range(len(cn)):
+            q = float(cw[a]) / int(cn[a]) if cn[a] else 0.0
+            mark = "  <-" if a == int(res["action"][0]) else ""
+            lines.append(f"{a:6d} {int(cn[a]):6d} {q:+8.3f} {float(cp[a]):6.3f}{mark}")
+        k = int(res["pv_len"][0])
+        end = ("cut at the length asked for", "no child with enough visits", "the game ends")[int(res["pv_end"][0])]
+        pv = zip(res["pv"][0][:k].tolist(), res["pv_n"][0][:k].tolist())
+        lines.append("pv: " + " ".join(f"{a}({n})" for a, n in pv) + f"  [{end}]")
+        lines.append(view.render(max_depth=tree_depth, min_visits=min_visits))
+        if view.truncated:
+            lines.append(f"({view.count} nodes qualify, {len(view)} shown)")
+        res = dict(res, view=view, text="\n".join(lines))
+        if out is not None:
+            out(res["text"])
+        return res
+
     def accumulate(self, pairs, breakdowns):
         """Add each pairing's breakdown ({"first": {...}, "second": {...}} in the first model's view) to
         results.json."""
@@ -442,7 +488,7 @@ def main(argv=None):
     from .envs import Connect4Env, TicTacToeEnv
 
     parser = argparse.ArgumentParser(description="rate registered models (the reference's main.py commands)")
-    parser.add_argument("command", choices=["compare_models", "calculate_elo", "grade", "observe"])
+    parser.add_argument("command", choices=["compare_models", "calculate_elo", "grade", "observe", "analyse"])
     parser.add_argument("--dir", required=True, help="the ModelDatabase directory")
     parser.add_argument("--g", dest="game", default="connect4", choices=["connect4", "tictactoe"])
     parser.add_argument("--b", nargs="*", dest="board_size", help="board size: W H")
@@ -455,6 +501,11 @@ def main(argv=None):
                         help="compare_models: keep every game's moves in <dir>/games/<key>.json")
     parser.add_argument("--max-empty", type=int, default=12,
                         help="grade: the exact solver takes the positions with at most this many empty cells")
+    parser.add_argument("--moves", nargs="*", type=int, default=[],
+                        help="analyse: the position, moves from the empty board")
+    parser.add_argument("--pv", type=int, default=8, help="analyse: principal variation length")
+    parser.add_argument("--tree-depth", type=int, default=2, help="analyse: depth the tree is shown to")
+    parser.add_argument("--min-visits", type=int, default=2, help="analyse: fewest visits of a node shown")
     args = parser.parse_args(argv)
     env = {"connect4": Connect4Env, "tictactoe": TicTacToeEnv}[args.game](*[int(x) for x in args.board_size or []])
     elo = Elo(ModelDatabase(args.dir, env))
@@ -466,6 +517,11 @@ def main(argv=None):
         if not args.p or len(args.p) != 2:
             parser.error("observe needs --p with two model names")
         elo.observe(*args.p, openings=args.openings)
+    elif args.command == "analyse":
+        if not args.p or len(args.p) != 1:
+            parser.error("analyse needs --p with one model name")
+        elo.analyse(args.p[0], args.moves, pv_len=args.pv, tree_depth=args.tree_depth, min_visits=args.min_visits,
+                    out=print)
     else:
         names = args.p or list(elo.model_database.models().keys())
         print(json.dumps(elo.compare_models(*names, num_games=args.games, openings=args.openings,

@@ -201,6 +201,31 @@ class MCTreeSearch(Policy):
     def root_node(self):
         return RootView(self._arena.root_stats(0))
 
+    def principal_variation(self, max_len=None, min_visits=1):
+        """The line the search expects from the active root, [(action, n, q), ...]: at each node the most visited
+        child, the lowest action on ties (the rule of _play's fallback, mcts.py:290-295), while it has at least
+        max(min_visits, 1) visits, for at most max_len moves (Arena.pv_batch).  q is MCNode.q of the child."""
+        out = {k: v[0].cpu().numpy() for k, v in self._arena.pv_batch([0], max_len, min_visits).items()}
+        self._arena.check()
+        pv = []
+        for k in range(int(out["pv_len"])):
+            n, vl, w = int(out["pv_n"][k]), int(out["pv_vl"][k]), float(out["pv_w"][k])
+            pv.append((int(out["pv"][k]), n, (w - vl) / (n + vl) if n + vl else 0))
+        return pv
+
+    def tree(self, min_visits=1, max_depth=None):
+        """The subtree under the active root as a tree.TreeView (the reference's root_node.children[a].children[b]
+        walk and RenderTree, on a host copy): the nodes with at least min_visits visits, to max_depth.  Sized for
+        one search's expansions first; a tree that does not fit is exported once more at its reported count."""
+        from .tree import TreeView
+
+        room = 2 + self.iterations * (self.actions if min_visits <= 0 else 1)
+        view = TreeView.from_export(self._arena.export_subtrees([0], room, min_visits, max_depth))
+        if view.truncated:
+            view = TreeView.from_export(self._arena.export_subtrees([0], view.count, min_visits, max_depth))
+        self._arena.check()
+        return view
+
     # ------------------------------------------------------------------ memory / training
     def update(self, s, a, r, done, next_s):
         self.push_to_queue(s, a, r, done, next_s)
@@ -267,7 +292,8 @@ class MCTreeSearch(Policy):
 
 @torch.no_grad()
 def analyse_positions(game, network, positions, iterations, search_threads=1, x_noise=0.25, seed=0, alpha=1.0,
-                      strong_play=False, cpuct=4.0, player=1, device=None, dtype=torch.float16, rng="philox"):
+                      strong_play=False, cpuct=4.0, player=1, device=None, dtype=torch.float16, rng="philox",
+                      pv_len=0, tree=None):
     """The search's answer for a batch of positions, each a move sequence from the empty board.
 
     One tree-mode arena of one tree per position: reset(player), one play_action step per ply (a tree whose
@@ -276,7 +302,13 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
     search() leaves it in; tree t draws from Philox subsequence t of `seed`.  Returns device tensors: child_n int32
     [n, A] (visit counts), child_w float64 [n, A], child_p float32 [n, A] (priors), root_n, root_w, root_q float64
     [n] (w / n of the root, 0 where n is 0), root_player int8 [n], action int64 [n] (the most visited child, the
-    lowest index on ties), board int8 [n, W, H] (tree frame)."""
+    lowest index on ties), board int8 [n, W, H] (tree frame).
+
+    pv_len > 0 adds each position's principal variation of at most pv_len moves (Arena.pv_batch): pv int8 [n,
+    pv_len] (-1 past the end; pv[:, 0] is `action` wherever the root was searched), pv_len int32 [n], pv_n int32 and
+    pv_w float64 [n, pv_len], pv_end uint8 [n].  A position's moves followed by its pv is a move list again.
+    tree=dict(max_nodes=, min_visits=, max_depth=) adds Arena.export_subtrees' arrays of every position under
+    "tree" (tree.TreeView.from_export(out["tree"], i) for position i).  Neither changes the other keys."""
     from .openings import validate_openings
 
     game = game if isinstance(game, str) else game_of_env(game)
@@ -310,6 +342,11 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
         rn = out["root_n"].to(torch.float64)
         out["root_q"] = torch.where(rn > 0, out["root_w"] / rn.clamp(min=1), torch.zeros_like(rn))
         out["action"] = out["child_n"].argmax(dim=1) if n else torch.zeros(0, dtype=torch.int64, device=dev)
+        if pv_len > 0:
+            pv = arena.pv_batch(trees, pv_len)
+            out.update(pv=pv["pv"], pv_len=pv["pv_len"], pv_n=pv["pv_n"], pv_w=pv["pv_w"], pv_end=pv["pv_end"])
+        if tree is not None:
+            out["tree"] = arena.export_subtrees(trees, **tree)
         arena.check()
     finally:
         arena.close()
