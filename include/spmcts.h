@@ -304,6 +304,21 @@ int spmcts_tree_export_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t 
                              int16_t *depth_dev, int32_t *node_n_dev, int32_t *node_vl_dev, double *node_w_dev,
                              float *node_p_dev, int8_t *player_dev, uint8_t *flags_dev, int32_t *count_dev,
                              void *work_dev, uint64_t work_bytes, spmcts_stream stream);
+/* What each of the n listed trees proves about the exact score s of its root position ("exact solver to the end
+ * of the game" below: e, the position's empty cells, if a move wins, 0 if it fills the board, else -s(child),
+ * maximised over the legal moves), queued on the stream with no host synchronisation: a minimax over the stored
+ * tree (score-bounded MCTS).  A legal move that ends the game is worth e or 0; a move into a node with a child
+ * block is worth [-hi(child), -lo(child)]; any other move [-(e - 1), e - 2]; a node's lo / hi are the maxima over
+ * its legal moves.  A root without a child block has its moves classified from the board alone.  The root must be
+ * unfinished, as for the solvers.  Per tree i: lo, hi int8 [n], lo <= s <= hi (lo == hi: solved); move_lo,
+ * move_hi int8 [n][A], the same per root move (-128 in both for an illegal move); best int8 [n], the lowest action
+ * with move_lo == lo (it secures lo); empty int8 [n], e of the root; nodes int32 [n], the expanded nodes the walk
+ * entered.  Any output may be NULL.  The walk's stack lives in the kernel's LDS: there is no work buffer.  A tree
+ * id outside the arena raises SPMCTS_ERR_STATE and leaves its row untouched (so does a store whose blocks do not
+ * form a tree).  -1: null handle / trees; -3: n < 0; n == 0 launches nothing. */
+int spmcts_tree_bounds_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n, int8_t *lo_dev, int8_t *hi_dev,
+                             int8_t *move_lo_dev, int8_t *move_hi_dev, int8_t *best_dev, int8_t *empty_dev,
+                             int32_t *nodes_dev, spmcts_stream stream);
 
 /* ---- games-level API (SelfPlayer.play_episode state machine) -------------- */
 /* Start games in the listed slots (selfplayworker.py:172-179): both trees reset,

@@ -18,7 +18,8 @@ exact depth-limited solver (solve_positions, tactical_report), and the exact sol
 (games/algos/evaluation_worker.py) on top of it, and game records (records.py: GameRecords, the move lists the
 arenas' games leave behind with record_games=True; grade_games, their moves held against the exact solvers), and
 the search trees below the root (tree.py: TreeView over Arena.export_subtrees; Arena.pv_batch,
-MCTreeSearch.principal_variation / .tree).
+MCTreeSearch.principal_variation / .tree), and what a search tree has proved about its position (Arena.bounds_batch,
+MCTreeSearch.score_bounds, TreeView.score_bounds; tree.py: bounds_to_codes, classify_bounds, describe_bounds).
 """
 from .base_model import BasePlayer, ModelContainer, Policy, TrainableModel  # noqa: F401
 from .memory import Memory  # noqa: F401
@@ -45,6 +46,9 @@ _LAZY = {
     "GameRecords": ".records",
     "grade_games": ".records",
     "TreeView": ".tree",
+    "bounds_to_codes": ".tree",
+    "classify_bounds": ".tree",
+    "describe_bounds": ".tree",
     "enumerate_openings": ".openings",
     "validate_openings": ".openings",
     "SelfPlayScheduler": ".self_play_parallel",

@@ -128,6 +128,7 @@ _SIGS = {
     "spmcts_tree_pv_batch": [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "spmcts_tree_export_work_bytes": [_P, _I32, _I32, ctypes.POINTER(_U64)],
     "spmcts_tree_export_batch": [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P],
+    "spmcts_tree_bounds_batch": [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
     "spmcts_set_league": [_P, _P, _I32],
     "spmcts_league_segments": [_P, _P],
     "spmcts_league_route": [_P, _P, _P, _I32, _P, _P, _P],

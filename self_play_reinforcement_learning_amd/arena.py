@@ -459,6 +459,25 @@ class Arena:
         self._export_keep = (t, work)  # alive until the kernel has run
         return out
 
+    BOUNDS_FIELDS = ("lo", "hi", "move_lo", "move_hi", "best", "empty", "nodes")
+
+    def bounds_batch(self, trees):
+        """What the listed trees (a list or a device int32 tensor) prove about the exact score s of their root
+        positions, as device tensors, queued on the current stream without a host synchronisation (include/spmcts.h
+        spmcts_tree_bounds_batch): a minimax over each stored tree in which an unexpanded node may still be worth
+        anything.  lo, hi int8 [n]: lo <= s <= hi (lo == hi: the search has solved the position); move_lo, move_hi
+        int8 [n, A]: the same per root move, -128 in both for an illegal move; best int8 [n]: the lowest action with
+        move_lo == lo; empty int8 [n]: the root's empty cells; nodes int32 [n]: the expanded nodes walked.
+        tree.bounds_to_codes turns the values into the solvers' move codes, tree.classify_bounds names the case."""
+        t = trees.to(self.device, torch.int32).contiguous() if torch.is_tensor(trees) else self._dev_i32(trees)
+        n, dev = int(t.numel()), self.device
+        i8 = lambda *shape: torch.full(shape, -128, dtype=torch.int8, device=dev)  # noqa: E731
+        out = dict(lo=i8(n), hi=i8(n), move_lo=i8(n, self.A), move_hi=i8(n, self.A), best=i8(n), empty=i8(n),
+                   nodes=torch.zeros(n, dtype=torch.int32, device=dev))
+        call("spmcts_tree_bounds_batch", self.h, ptr(t), n, *[ptr(out[k]) for k in self.BOUNDS_FIELDS], _stream())
+        self._bounds_trees = t  # alive until the kernel has run
+        return out
+
     # ------------------------------------------------------------------ games API
     def games_set_openings(self, openings, id_period=0):
         """The arena's opening book (include/spmcts.h spmcts_games_set_openings): `openings` a list of move

@@ -1,19 +1,20 @@
-// arena_tree.h — reading the search trees below the root: k_tree_pv (principal variations) and k_tree_export
-// (subtrees in breadth-first order).  Included by spmcts.hip after arena_games.h: needs View, the node accessors,
-// set_err, nbase and board.h's step.
+// arena_tree.h — reading the search trees below the root: k_tree_pv (principal variations), k_tree_export
+// (subtrees in breadth-first order) and k_tree_bounds (what a tree proves: bounds on the exact score).  Included by
+// spmcts.hip after arena_games.h: needs View, the node accessors, set_err, nbase and board.h's step.
 //
-// Both kernels only read the arena (the one write is set_err for a tree id outside [0, T), whose outputs are
+// The kernels only read the arena (the one write is set_err for a tree id outside [0, T), whose outputs are
 // left untouched) and take one APAD-lane group per listed tree as k_root_stats_batch does (lane j: child j of the
 // node under inspection).  Reductions inside a group are cross-lane only -- arena_select.h's DPP argmax, and
-// ballot plus popcount under the group's lane mask -- with no LDS and no atomics on the outputs, so the layout is a
-// function of the tree; every loop is bounded by an argument or a board constant.  A child-block index read from
-// the store is used only inside [0, cap): anything else counts as "no block".
+// ballot plus popcount under the group's lane mask -- with no atomics on the outputs, so the layout is a function
+// of the tree (LDS holds k_tree_bounds' stack and nothing else); every loop is bounded by an argument, a board
+// constant or cap.  A child-block index read from the store is used only inside [0, cap): anything else counts as
+// "no block".
 // (No __shfl / __shfl_xor here: they are shared inline functions of the HIP headers, and a new caller in this
 // translation unit changed the code hipcc generates for k_expand_vl and k_select_vl, which also call them.  With
 // the DPP argmax and the ballots the other kernels' assembly is what it was: scripts/product_isa_equal.sh.)
 //
 // The virtual loss is a stored field of K > 1 arenas only (reset_tree, k_expand_vl); a sequential arena never
-// writes the vl words, and MCNode.virtual_loss is 0 outside search_node there: both kernels report 0.
+// writes the vl words, and MCNode.virtual_loss is 0 outside search_node there: k_tree_pv and k_tree_export report 0.
 
 // pointers of spmcts_tree_pv_batch's outputs ([n][max_len] unless noted; any may be null)
 struct TreePvOut {
@@ -253,4 +254,150 @@ __global__ void k_tree_export(View v, const int32_t *trees, int n, int max_nodes
     }
   }
   if (lane == 0 && o.count) o.count[i] = count;
+}
+
+// ---- score bounds ------------------------------------------------------------
+// pointers of spmcts_tree_bounds_batch's outputs ([n] unless noted; any may be null)
+struct TreeBoundsOut {
+  int8_t *lo, *hi;
+  int8_t *move_lo, *move_hi;  // [n][A]
+  int8_t *best, *empty;
+  int32_t *nodes;
+};
+
+enum { TB_THREADS = 64, TB_NONE = -128 };
+
+// the largest x of the group, in every lane
+template <int P>
+__device__ __forceinline__ int group_max(int x) {
+  static_assert(P == 8 || P == 16, "tree groups of 8 or 16 lanes");
+  x = max(x, dpp_i<DPP_XOR1>(x));
+  x = max(x, dpp_i<DPP_XOR2>(x));
+  x = max(x, dpp_i<DPP_HALF_MIRROR>(x));
+  if constexpr (P == 16) x = max(x, dpp_i<DPP_MIRROR>(x));
+  return x;
+}
+
+// A frame's third word: child block | children still to descend into << 32 | (lo + 128) << 48 | (hi + 128) << 56.
+__device__ __forceinline__ uint64_t bounds_pack(int cb, uint32_t dm, int lo, int hi) {
+  return (uint64_t)(uint32_t)cb | ((uint64_t)(dm & 0xffffu) << 32) | ((uint64_t)((uint32_t)(lo + 128) & 0xffu) << 48) |
+         ((uint64_t)((uint32_t)(hi + 128) & 0xffu) << 56);
+}
+
+// The node (board b, mover `player`, child block cb, e empty cells) as the walk enters it: lane j classifies move
+// j.  A move is legal iff step accepts it and places a stone (on the free-placement board step passes over an
+// occupied cell in silence).  A legal move that ends the game is worth e (a win) or 0 (the board is full); one
+// into a child with a child block is left to the walk (its bit in dm) while the stack has a level for it; any
+// other is worth the trivial bounds of a position of e - 1 empty cells seen from this side.  mlo / mhi: lane j's
+// move (TB_NONE: illegal, or left to the walk); lo / hi: their maxima over the group.
+template <class G>
+__device__ __forceinline__ void bounds_enter(const View &v, size_t nb, Board b, int player, int cb, int lane,
+                                             bool room, int &mlo, int &mhi, int &lo, int &hi, uint32_t &dm) {
+  constexpr int P = G::APAD;
+  const uint64_t occ = b.pos | b.neg;
+  const int e = G::CELLS - popc(occ);
+  mlo = mhi = TB_NONE;
+  bool desc = false;
+  if (lane < G::A) {
+    Board nbd = b;
+    int rew = 0, done = 0;
+    if (step<G>(nbd, lane, player, &rew, &done) == STEP_OK && (nbd.pos | nbd.neg) != occ) {
+      if (done) {
+        mlo = mhi = rew ? e : 0;
+      } else {
+        const int cc = tree_block_ok(v, cb) ? nd_c<P>(v, nb + (size_t)cb * P + lane) : -1;
+        if (tree_block_ok(v, cc) && room) {
+          desc = true;
+        } else {
+          mlo = -(e - 1);
+          mhi = e - 2;
+        }
+      }
+    }
+  }
+  lo = group_max<P>(mlo);
+  hi = group_max<P>(mhi);
+  dm = group_ballot<P>(desc);
+}
+
+// What each listed tree proves about the exact score s of its root position (solve.h's s: e if a move wins, 0 if
+// it fills the board, else -s(child), maximised over the legal moves): lo <= s <= hi, by a minimax over the stored
+// tree with every unexpanded node open.  Depth-first and iterative: the node in hand lives in registers (the same
+// values in every lane of the group), its ancestors in the block's LDS, one frame of three 8-byte words per level,
+// level-major so that the groups of a wave sit in neighbouring banks.  Every lane of a group writes the same words
+// to the same addresses and reads back what it wrote itself, so no lane waits for another.  A round leaves the node
+// in hand for its parent or descends into its next expanded child: each expanded node is entered once and left
+// once, at most 2 * cap rounds in a sound store.  A walk that is not over by then has met a store that is no tree:
+// SPMCTS_ERR_STATE, and its row is left untouched.
+template <class G>
+__global__ __launch_bounds__(TB_THREADS) void k_tree_bounds(View v, const int32_t *trees, int n, TreeBoundsOut o) {
+  constexpr int P = G::APAD, GPB = TB_THREADS / P, LEVELS = G::CELLS + 1;
+  __shared__ uint64_t s_stk[LEVELS][3][GPB];
+  const int t = blockIdx.x * TB_THREADS + threadIdx.x;
+  const int i = t / P, lane = t % P, grp = threadIdx.x / P;
+  if (i >= n) return;
+  const int tree = trees[i];
+  if (tree < 0 || tree >= v.T) {
+    if (lane == 0) set_err(v, SPMCTS_ERR_STATE);
+    return;
+  }
+  const size_t nb = nbase<G>(v, tree);
+  const int rplayer = v.rplayer[tree];
+  Board b{v.rpos[tree], v.rneg[tree]};
+  const int e0 = G::CELLS - popc(b.pos | b.neg);
+  int cb = nd_c<P>(v, nb + v.root[tree]);
+  int sp = 0, nodes = tree_block_ok(v, cb) ? 1 : 0, root_a = -1;
+  int rmlo, rmhi, lo, hi;  // rmlo / rmhi: the root's move of this lane
+  uint32_t dm;
+  bounds_enter<G>(v, nb, b, rplayer, cb, lane, true, rmlo, rmhi, lo, hi, dm);
+  bool over = false;
+  for (int it = 0; it <= 2 * v.cap; ++it) {
+    if (dm == 0) {  // the node in hand is done: its bounds go to its parent, negated
+      if (sp == 0) {
+        over = true;
+        break;
+      }
+      const int clo = lo, chi = hi;
+      --sp;
+      const uint64_t w = s_stk[sp][2][grp];
+      b = Board{s_stk[sp][0][grp], s_stk[sp][1][grp]};
+      cb = (int32_t)(uint32_t)w;
+      dm = (uint32_t)(w >> 32) & 0xffffu;
+      lo = max((int)((w >> 48) & 0xffu) - 128, -chi);
+      hi = max((int)((w >> 56) & 0xffu) - 128, -clo);
+      if (sp == 0 && lane == root_a) {
+        rmlo = -chi;
+        rmhi = -clo;
+      }
+    } else {  // descend into the next expanded child
+      const int a = __ffs((int)dm) - 1;
+      dm &= dm - 1u;
+      s_stk[sp][0][grp] = b.pos;
+      s_stk[sp][1][grp] = b.neg;
+      s_stk[sp][2][grp] = bounds_pack(cb, dm, lo, hi);
+      if (sp == 0) root_a = a;
+      play<G>(b, a, (sp & 1) ? -rplayer : rplayer);
+      cb = nd_c<P>(v, nb + (size_t)cb * P + a);  // (inside [0, cap): bounds_enter set the bit)
+      ++sp;
+      ++nodes;
+      int mlo, mhi;
+      bounds_enter<G>(v, nb, b, (sp & 1) ? -rplayer : rplayer, cb, lane, sp + 1 < LEVELS, mlo, mhi, lo, hi, dm);
+    }
+  }
+  if (!over) {
+    if (lane == 0) set_err(v, SPMCTS_ERR_STATE);
+    return;
+  }
+  if (lane < G::A) {
+    if (o.move_lo) o.move_lo[(size_t)i * G::A + lane] = (int8_t)rmlo;
+    if (o.move_hi) o.move_hi[(size_t)i * G::A + lane] = (int8_t)rmhi;
+  }
+  const uint32_t secure = group_ballot<P>(rmlo != TB_NONE && rmlo == lo);
+  if (lane == 0) {
+    if (o.lo) o.lo[i] = (int8_t)lo;
+    if (o.hi) o.hi[i] = (int8_t)hi;
+    if (o.best) o.best[i] = (int8_t)(__ffs((int)secure) - 1);
+    if (o.empty) o.empty[i] = (int8_t)e0;
+    if (o.nodes) o.nodes[i] = nodes;
+  }
 }

@@ -34,7 +34,8 @@
 //   negamax.h       exact depth-limited negamax: the search core (host and device), its batch and arena kernels
 //   solve.h         exact solver to the end of the game: alpha-beta with a transposition table, resumable launches
 //   arena_games.h   game state machine (opening book plies included), the hard-coded players, k_root_stats_batch, export
-//   arena_tree.h    reading the trees below the root: k_tree_pv (principal variations), k_tree_export (subtrees)
+//   arena_tree.h    reading the trees below the root: k_tree_pv (principal variations), k_tree_export (subtrees),
+//                   k_tree_bounds (what a tree proves: bounds on the exact score)
 //   records.h       game records (move lists) to the positions before their moves: spmcts_log_positions and its host twin
 //   arena_misc.h    k_env_step, k_table_net, k_copy_probe, the init kernels
 //   arena_league.h  league routing: a step's rows partitioned by their tree's network, and back
@@ -1230,6 +1231,17 @@ int spmcts_tree_export_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t 
                         flags_dev, count_dev};
   return LAUNCH(h, k_tree_export, (long long)n * h->P, 256, (hipStream_t)stream, h->v, trees_dev, n, max_nodes,
                 min_visits, max_depth, o, (uint64_t *)work_dev);
+}
+
+int spmcts_tree_bounds_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n, int8_t *lo_dev, int8_t *hi_dev,
+                             int8_t *move_lo_dev, int8_t *move_hi_dev, int8_t *best_dev, int8_t *empty_dev,
+                             int32_t *nodes_dev, spmcts_stream stream) {
+  if (!h) return fail(-1, "null arena");
+  if (n < 0) return fail(-3, "tree_bounds: n must not be negative");
+  if (n == 0) return 0;
+  if (!trees_dev) return fail(-1, "null argument");
+  const TreeBoundsOut o{lo_dev, hi_dev, move_lo_dev, move_hi_dev, best_dev, empty_dev, nodes_dev};
+  return LAUNCH(h, k_tree_bounds, (long long)n * h->P, TB_THREADS, (hipStream_t)stream, h->v, trees_dev, n, o);
 }
 
 // ---- league ---------------------------------------------------------------

@@ -413,15 +413,17 @@ class Elo:
             out("")
         return records
 
-    def analyse(self, name, moves, pv_len=8, tree_depth=2, min_visits=2, out=None):
+    def analyse(self, name, moves, pv_len=8, tree_depth=2, min_visits=2, out=None, bounds=False):
         """One registered MCTreeSearch model's search of the position after `moves` (a move list from the empty
         board): mcts.analyse_positions with the model's own iterations / alpha / strong_play, its principal
         variation of at most pv_len moves and its tree to tree_depth (nodes with at least min_visits visits).
         Returns analyse_positions' dict for the one position plus "view" (the tree.TreeView) and "text" (the root
-        table, the PV and the rendered tree); out (e.g. print) receives the text."""
+        table, the PV and the rendered tree); out (e.g. print) receives the text.  bounds=True adds what the
+        search's tree has proved about the position (Arena.bounds_batch; analyse_positions' bound_* keys) and one
+        more line of text, e.g. "proved: win in 5 by 3" or "bounds: at least a draw" (tree.describe_bounds)."""
         from .arena import game_of_env
         from .mcts import analyse_positions
-        from .tree import TreeView
+        from .tree import TreeView, describe_bounds
 
         entry = self.model_database.models()[name]
         if entry["policy"] != "MCTreeSearch":
@@ -433,7 +435,7 @@ class Elo:
                                 search_threads=self.search_threads, seed=self.seed, alpha=float(kw.get("alpha", 1)),
                                 strong_play=bool(kw.get("strong_play", False)), device=self.device, dtype=self.dtype,
                                 pv_len=int(pv_len), tree=dict(max_nodes=2 + its, min_visits=int(min_visits),
-                                                              max_depth=tree_depth))
+                                                              max_depth=tree_depth), bounds=bool(bounds))
         view = TreeView.from_export(res["tree"], 0)
         cn, cw, cp = (res[k][0].cpu().numpy() for k in ("child_n", "child_w", "child_p"))
         lines = [f"{name}: {its} simulations after moves {list(moves)}; root n={int(res['root_n'][0])} "
@@ -450,6 +452,10 @@ class Elo:
         lines.append(view.render(max_depth=tree_depth, min_visits=min_visits))
         if view.truncated:
             lines.append(f"({view.count} nodes qualify, {len(view)} shown)")
+        if bounds:
+            empty = int((res["board"][0] == 0).sum())
+            lines.append(describe_bounds(int(res["bound_lo"][0]), int(res["bound_hi"][0]), empty,
+                                         int(res["bound_best"][0])))
         res = dict(res, view=view, text="\n".join(lines))
         if out is not None:
             out(res["text"])
@@ -506,6 +512,8 @@ def main(argv=None):
     parser.add_argument("--pv", type=int, default=8, help="analyse: principal variation length")
     parser.add_argument("--tree-depth", type=int, default=2, help="analyse: depth the tree is shown to")
     parser.add_argument("--min-visits", type=int, default=2, help="analyse: fewest visits of a node shown")
+    parser.add_argument("--bounds", action="store_true",
+                        help="analyse: add what the search's tree has proved about the position")
     args = parser.parse_args(argv)
     env = {"connect4": Connect4Env, "tictactoe": TicTacToeEnv}[args.game](*[int(x) for x in args.board_size or []])
     elo = Elo(ModelDatabase(args.dir, env))
@@ -521,7 +529,7 @@ def main(argv=None):
         if not args.p or len(args.p) != 1:
             parser.error("analyse needs --p with one model name")
         elo.analyse(args.p[0], args.moves, pv_len=args.pv, tree_depth=args.tree_depth, min_visits=args.min_visits,
-                    out=print)
+                    out=print, bounds=args.bounds)
     else:
         names = args.p or list(elo.model_database.models().keys())
         print(json.dumps(elo.compare_models(*names, num_games=args.games, openings=args.openings,

@@ -226,6 +226,24 @@ class MCTreeSearch(Policy):
         self._arena.check()
         return view
 
+    def score_bounds(self):
+        """What the tree under the active root has proved about its position (Arena.bounds_batch): lo <= s <= hi
+        for the exact solver's score s (solve.py), per root move move_lo / move_hi (-128: illegal), best (the
+        lowest action that secures lo), empty, nodes; status, tree.classify_bounds(lo, hi): "win", "loss", "draw",
+        "not_lost", "not_won" or "open"; and the bounds as the solvers' move codes (tree.bounds_to_codes: +k a
+        win in k plies, -k a loss at ply k): lo_code, hi_code, move_lo_code, move_hi_code.  Plain ints and lists."""
+        from .tree import bounds_to_codes, classify_bounds
+
+        raw = {k: v[0].cpu().numpy() for k, v in self._arena.bounds_batch([0]).items()}
+        self._arena.check()
+        out = {k: (v.tolist() if v.ndim else int(v)) for k, v in raw.items()}
+        e = out["empty"]
+        out["status"] = classify_bounds(out["lo"], out["hi"])
+        out.update(lo_code=bounds_to_codes(out["lo"], e), hi_code=bounds_to_codes(out["hi"], e),
+                   move_lo_code=bounds_to_codes(raw["move_lo"], e).tolist(),
+                   move_hi_code=bounds_to_codes(raw["move_hi"], e).tolist())
+        return out
+
     # ------------------------------------------------------------------ memory / training
     def update(self, s, a, r, done, next_s):
         self.push_to_queue(s, a, r, done, next_s)
@@ -293,7 +311,7 @@ class MCTreeSearch(Policy):
 @torch.no_grad()
 def analyse_positions(game, network, positions, iterations, search_threads=1, x_noise=0.25, seed=0, alpha=1.0,
                       strong_play=False, cpuct=4.0, player=1, device=None, dtype=torch.float16, rng="philox",
-                      pv_len=0, tree=None):
+                      pv_len=0, tree=None, bounds=False):
     """The search's answer for a batch of positions, each a move sequence from the empty board.
 
     One tree-mode arena of one tree per position: reset(player), one play_action step per ply (a tree whose
@@ -308,7 +326,9 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
     pv_len] (-1 past the end; pv[:, 0] is `action` wherever the root was searched), pv_len int32 [n], pv_n int32 and
     pv_w float64 [n, pv_len], pv_end uint8 [n].  A position's moves followed by its pv is a move list again.
     tree=dict(max_nodes=, min_visits=, max_depth=) adds Arena.export_subtrees' arrays of every position under
-    "tree" (tree.TreeView.from_export(out["tree"], i) for position i).  Neither changes the other keys."""
+    "tree" (tree.TreeView.from_export(out["tree"], i) for position i).  bounds=True adds what each position's tree
+    has proved (Arena.bounds_batch): bound_lo, bound_hi int8 [n] (lo <= s <= hi for the exact solver's score s),
+    move_lo, move_hi int8 [n, A], bound_best int8 [n], bound_nodes int32 [n].  None of them changes the other keys."""
     from .openings import validate_openings
 
     game = game if isinstance(game, str) else game_of_env(game)
@@ -347,6 +367,10 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
             out.update(pv=pv["pv"], pv_len=pv["pv_len"], pv_n=pv["pv_n"], pv_w=pv["pv_w"], pv_end=pv["pv_end"])
         if tree is not None:
             out["tree"] = arena.export_subtrees(trees, **tree)
+        if bounds:
+            b = arena.bounds_batch(trees)
+            out.update(bound_lo=b["lo"], bound_hi=b["hi"], move_lo=b["move_lo"], move_hi=b["move_hi"],
+                       bound_best=b["best"], bound_nodes=b["nodes"])
         arena.check()
     finally:
         arena.close()

@@ -17,6 +17,59 @@ import numpy as np
 
 FLAG_EXPANDED, FLAG_VALID, FLAG_TERMINAL = 1, 2, 4
 FIELDS = ("parent", "action", "depth", "node_n", "node_vl", "node_w", "node_p", "player", "flags")
+BOUND_ILLEGAL = -128  # move_lo / move_hi of an illegal move, and its code
+
+
+def bounds_to_codes(values, empty):
+    """Score bounds (Arena.bounds_batch's lo, hi, move_lo, move_hi: values of the exact score s) as the solvers'
+    move codes at a root of `empty` empty cells: e + 1 - v for v > 0 (a win in that many plies), -(e + 1 + v) for
+    v < 0 (a loss at that ply), 0 for 0, -128 kept.  values: an int, a list, a numpy array or a tensor, `empty`
+    broadcast over its last axis ([n] against [n, A]); an int gives an int, anything else a numpy int8 array."""
+    scalar = isinstance(values, (int, np.integer))
+    v = np.asarray(values.cpu() if hasattr(values, "cpu") else values).astype(np.int64)
+    e = np.asarray(empty.cpu() if hasattr(empty, "cpu") else empty).astype(np.int64)
+    if v.ndim > e.ndim:
+        e = e.reshape(e.shape + (1,) * (v.ndim - e.ndim))
+    code = np.where(v == BOUND_ILLEGAL, BOUND_ILLEGAL, np.where(v > 0, e + 1 - v, np.where(v < 0, -(e + 1 + v), 0)))
+    return int(code) if scalar else code.astype(np.int8)
+
+
+def classify_bounds(lo, hi):
+    """What lo <= s <= hi says about the side to move: "win" (lo > 0), "loss" (hi < 0), "draw" (lo == hi == 0),
+    "not_lost" (lo == 0 < hi), "not_won" (lo < 0 == hi), else "open"."""
+    lo, hi = int(lo), int(hi)
+    if lo > 0:
+        return "win"
+    if hi < 0:
+        return "loss"
+    if lo == 0:
+        return "draw" if hi == 0 else "not_lost"
+    return "not_won" if hi == 0 else "open"
+
+
+def describe_bounds(lo, hi, empty, best):
+    """One line on what a tree has proved: "proved: win in 5 by 3" (a forced win in 5 plies, secured by action 3),
+    "proved: loss in 4", "proved: draw by 2", "bounds: at least a draw", "bounds: at most a draw", "bounds: open".
+    Where a win or a loss is proved but its length is not (lo < hi), the ply count is the bound's: "in at most"."""
+    status = classify_bounds(lo, hi)
+    exact = "" if int(lo) == int(hi) else "at most "
+    if status == "win":
+        return f"proved: win in {exact}{bounds_to_codes(int(lo), int(empty))} by {int(best)}"
+    if status == "loss":
+        return f"proved: loss in {exact}{-bounds_to_codes(int(hi), int(empty))}"
+    if status == "draw":
+        return f"proved: draw by {int(best)}"
+    return {"not_lost": "bounds: at least a draw", "not_won": "bounds: at most a draw", "open": "bounds: open"}[status]
+
+
+def _env_of(game):
+    from .arena import GAMES
+    from .envs import Connect4Env, TicTacToeEnv
+
+    if game not in GAMES:
+        raise ValueError(f"unknown game {game!r}")
+    _, W, H, A = GAMES[game]
+    return (TicTacToeEnv() if game == "tictactoe" else Connect4Env(W, H)), W, H, A
 
 
 class TreeNode:
@@ -119,6 +172,51 @@ class TreeView:
             out.append((best.action, best.n, best.q))
             node = best
         return out
+
+    def score_bounds(self, game, board, player):
+        """The host twin of Arena.bounds_batch (include/spmcts.h spmcts_tree_bounds_batch; no GPU): what this tree
+        proves about the exact score s of its root position, lo <= s <= hi.  game: the arena's game name; board
+        [W, H]: the root's board of +-1 stones; player: the side to move there.  The view must hold the whole tree:
+        exported with min_visits=0 and not truncated (ValueError otherwise).  A legal move (the env's valid_moves)
+        that ends the game is worth e, the root's empty cells, for a win and 0 for a full board; a move into an
+        expanded node [-hi(child), -lo(child)]; any other [-(e - 1), e - 2]; lo / hi are the maxima over the legal
+        moves.  Returns dict(lo, hi, move_lo [A], move_hi [A] (-128: illegal), best (the lowest action with
+        move_lo == lo), empty, nodes (the expanded nodes entered)), plain ints and lists."""
+        env, W, H, A = _env_of(game)
+        if self.truncated or self.root is None:
+            raise ValueError("score_bounds needs the whole tree: this view is truncated")
+        for nd in self.nodes:
+            if nd.expanded and [c.action for c in nd.children] != list(range(A)):
+                raise ValueError("score_bounds needs every child of every expanded node: export with min_visits=0")
+        entered = [0]
+
+        def walk(node, state, mover):
+            """(lo, hi, move_lo, move_hi) of `node`, whose board is `state` with `mover` to move."""
+            e = int((state == 0).sum())
+            entered[0] += node.expanded
+            env.set_state(state)
+            env.episode_over = False
+            legal = env.valid_moves()
+            mlo, mhi = [BOUND_ILLEGAL] * A, [BOUND_ILLEGAL] * A
+            for a in range(A):
+                if not legal[a]:
+                    continue
+                env.set_state(state.copy())
+                env.episode_over = False
+                s, r, done, _ = env.step(a, player=mover)
+                if done:
+                    mlo[a] = mhi[a] = e if r else 0
+                elif node.expanded and node.children[a].expanded:
+                    clo, chi, _, _ = walk(node.children[a], s.copy(), -mover)
+                    mlo[a], mhi[a] = -chi, -clo
+                else:
+                    mlo[a], mhi[a] = -(e - 1), e - 2
+            return max(mlo), max(mhi), mlo, mhi
+
+        state = np.array(board, dtype=np.int64).reshape(W, H)
+        lo, hi, mlo, mhi = walk(self.root, state, int(player))
+        best = mlo.index(lo) if lo != BOUND_ILLEGAL else -1
+        return dict(lo=lo, hi=hi, move_lo=mlo, move_hi=mhi, best=best, empty=int((state == 0).sum()), nodes=entered[0])
 
     def render(self, max_depth=None, min_visits=1):
         """One line per node in the style of anytree's RenderTree: action, n, q, p, `#` on a node whose move
