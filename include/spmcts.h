@@ -320,6 +320,44 @@ int spmcts_tree_bounds_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t 
                              int8_t *move_lo_dev, int8_t *move_hi_dev, int8_t *best_dev, int8_t *empty_dev,
                              int32_t *nodes_dev, spmcts_stream stream);
 
+/* ---- proof-guided play ------------------------------------------------------ */
+/* Let the move choice use what the tree has proved (off by default).  `on` uint8 [T]: the trees it is on for, or
+ * NULL: every tree.  Synchronises; the first call that switches a tree on allocates the arrays below.  Before a
+ * move is chosen (spmcts_games_end_ply: each active game's mover tree; spmcts_search_end: the active trees), the
+ * walk of spmcts_tree_bounds_batch gives the root's lo, hi and its moves' move_lo, move_hi, and the keep set
+ *   S = { legal a : move_lo[a] == lo }   if lo > 0 (a win is secured) or lo == hi (the root is solved),
+ *   S = { legal a : move_hi[a] >= lo }   otherwise (moves proved worse than what another secures are dropped).
+ * S is never empty and holds no illegal move.  The visit-count weights of the moves outside S are set to 0; if no
+ * move of S has a visit, each weighs 1; normalisation, validation, the one random draw and the argmax fallback (over
+ * S) are as without the feature, and the Move record takes the masked probabilities.  A tree whose flag is off, a
+ * tree of a hard-coded player and a game in its opening book choose as before, bit for bit. */
+int spmcts_set_proof_play(spmcts_arena *h, const uint8_t *on);
+/* The verdict of the n listed trees as they stand, queued on the stream with no host synchronisation, whatever
+ * their flags: keep uint32 [n] (bit a: move a is in S), lo, hi int8 [n].  Read-only, at any point of a search.  Any
+ * output may be NULL.  A tree id outside the arena raises SPMCTS_ERR_STATE and leaves its row untouched.
+ * -1: null handle / trees; -3: n < 0; n == 0 launches nothing. */
+int spmcts_tree_proof_moves_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n, uint32_t *keep_dev,
+                                  int8_t *lo_dev, int8_t *hi_dev, spmcts_stream stream);
+/* What the last spmcts_games_end_ply / spmcts_search_end wrote, per tree [T]: keep 0xffffffff (no restriction) and
+ * lo = hi = -128 for a tree the feature did not apply to; a tree that chose no move then keeps its earlier row.
+ * Any output may be NULL.  -4: proof play is off. */
+int spmcts_proof_last(spmcts_arena *h, uint32_t *keep_dev, int8_t *lo_dev, int8_t *hi_dev, spmcts_stream stream);
+/* Counts since the arrays were allocated, int64 [SPMCTS_PROOF_NSTAT] (synchronises): [0] plies chosen with the
+ * feature on, [1] those with a solved root, [2] with a secured win (lo > 0), [3] with S smaller than the legal
+ * set; [4] trees spmcts_proof_stop stopped, [5] the sims they did not start (limit - started at the stop). */
+enum { SPMCTS_PROOF_NSTAT = 6 };
+int spmcts_get_proof_stats(spmcts_arena *h, int64_t *out);
+/* A searching tree whose root is now solved (lo == hi) starts no more sims, queued on the stream with no host
+ * synchronisation, between two simulation steps: for every tree with proof play on that is searching (started <
+ * min(budget, iterations)) and not paused inside a fill by the sim cap (such a tree is looked at again by the next
+ * call), the walk; if lo == hi the tree is left as a search whose sims have all been started: its pending slots are
+ * replied by the following expands, it selects no more, and the move choice finds it complete.  Over the arena
+ * sims + leaked_sims + stats[5] == searches x iterations.  -4: search_threads <= 1, or proof play is off. */
+int spmcts_proof_stop(spmcts_arena *h, spmcts_stream stream);
+/* Per tree, int32 [T]: the searches of the tree that spmcts_proof_stop has stopped so far (their sum is stats[4]),
+ * queued on the stream with no host synchronisation; all 0 where proof play was never on. */
+int spmcts_proof_stopped(spmcts_arena *h, int32_t *count_dev, spmcts_stream stream);
+
 /* ---- games-level API (SelfPlayer.play_episode state machine) -------------- */
 /* Start games in the listed slots (selfplayworker.py:172-179): both trees reset,
  * swap_sides = game id odd (self_play_parallel.py:237).  Game ids continue from

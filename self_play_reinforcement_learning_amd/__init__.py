@@ -19,7 +19,9 @@ exact depth-limited solver (solve_positions, tactical_report), and the exact sol
 arenas' games leave behind with record_games=True; grade_games, their moves held against the exact solvers), and
 the search trees below the root (tree.py: TreeView over Arena.export_subtrees; Arena.pv_batch,
 MCTreeSearch.principal_variation / .tree), and what a search tree has proved about its position (Arena.bounds_batch,
-MCTreeSearch.score_bounds, TreeView.score_bounds; tree.py: bounds_to_codes, classify_bounds, describe_bounds).
+MCTreeSearch.score_bounds, TreeView.score_bounds; tree.py: bounds_to_codes, classify_bounds, describe_bounds), and
+playing it (proof_play= of MCTreeSearch / SelfPlayEngine / a LeagueEngine player: Arena.set_proof_play,
+proof_moves_batch, proof_last, proof_stats, proof_stop; tree.proof_move_set, the keep set's host twin).
 """
 from .base_model import BasePlayer, ModelContainer, Policy, TrainableModel  # noqa: F401
 from .memory import Memory  # noqa: F401
@@ -49,6 +51,7 @@ _LAZY = {
     "bounds_to_codes": ".tree",
     "classify_bounds": ".tree",
     "describe_bounds": ".tree",
+    "proof_move_set": ".tree",
     "enumerate_openings": ".openings",
     "validate_openings": ".openings",
     "SelfPlayScheduler": ".self_play_parallel",

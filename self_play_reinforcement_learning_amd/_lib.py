@@ -129,6 +129,12 @@ _SIGS = {
     "spmcts_tree_export_work_bytes": [_P, _I32, _I32, ctypes.POINTER(_U64)],
     "spmcts_tree_export_batch": [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P],
     "spmcts_tree_bounds_batch": [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
+    "spmcts_set_proof_play": [_P, _P],
+    "spmcts_tree_proof_moves_batch": [_P, _P, _I32, _P, _P, _P, _P],
+    "spmcts_proof_last": [_P, _P, _P, _P, _P],
+    "spmcts_get_proof_stats": [_P, _P],
+    "spmcts_proof_stop": [_P, _P],
+    "spmcts_proof_stopped": [_P, _P, _P],
     "spmcts_set_league": [_P, _P, _I32],
     "spmcts_league_segments": [_P, _P],
     "spmcts_league_route": [_P, _P, _P, _I32, _P, _P, _P],

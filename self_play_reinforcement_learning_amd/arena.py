@@ -478,6 +478,67 @@ class Arena:
         self._bounds_trees = t  # alive until the kernel has run
         return out
 
+    # ------------------------------------------------------------------ proof-guided play
+    PROOF_STATS = ("plies", "solved", "secured_win", "restricted", "trees_stopped", "sims_skipped")
+
+    def set_proof_play(self, on=True):
+        """Let the move choice use what the tree has proved (include/spmcts.h spmcts_set_proof_play): before a move
+        is chosen, the moves outside the tree's keep set (tree.proof_move_set of its score bounds) lose their visit
+        weight.  `on`: True / False for every tree, or one flag per tree.  Off by default; synchronises."""
+        torch.cuda.current_stream().synchronize()
+        if isinstance(on, (bool, int, np.bool_)):
+            flags = np.full(self.n_trees, 1 if on else 0, dtype=np.uint8)
+        else:
+            flags = np.ascontiguousarray(np.asarray(on, dtype=bool).astype(np.uint8))
+            if flags.shape != (self.n_trees,):
+                raise ValueError(f"expected {self.n_trees} per-tree entries, got {flags.shape}")
+        call("spmcts_set_proof_play", self.h, flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+        self.proof_play = flags.astype(bool)
+
+    def proof_moves_batch(self, trees):
+        """The verdict of the listed trees (a list or a device int32 tensor) as they stand, as device tensors,
+        queued on the current stream without a host synchronisation and at any point of a search
+        (spmcts_tree_proof_moves_batch): keep int32 [n], bit a set: move a is in the keep set (tree.proof_move_set of
+        bounds_batch's values); lo, hi int8 [n], the root's score bounds.  Whatever the trees' proof_play flags."""
+        t = trees.to(self.device, torch.int32).contiguous() if torch.is_tensor(trees) else self._dev_i32(trees)
+        n, dev = int(t.numel()), self.device
+        out = dict(keep=torch.full((n,), -1, dtype=torch.int32, device=dev),
+                   lo=torch.full((n,), -128, dtype=torch.int8, device=dev),
+                   hi=torch.full((n,), -128, dtype=torch.int8, device=dev))
+        call("spmcts_tree_proof_moves_batch", self.h, ptr(t), n, ptr(out["keep"]), ptr(out["lo"]), ptr(out["hi"]),
+             _stream())
+        self._proof_trees = t  # alive until the kernel has run
+        return out
+
+    def proof_last(self):
+        """What the last games_end_ply / search_end decided with, per tree, as device tensors (spmcts_proof_last):
+        keep int32 [T] (-1, all bits: no restriction -- the feature off for the tree, a hard-coded player, a book
+        ply), lo, hi int8 [T] (-128 beside -1).  A tree that chose no move keeps its earlier row."""
+        T, dev = self.n_trees, self.device
+        out = dict(keep=torch.empty(T, dtype=torch.int32, device=dev), lo=torch.empty(T, dtype=torch.int8, device=dev),
+                   hi=torch.empty(T, dtype=torch.int8, device=dev))
+        call("spmcts_proof_last", self.h, ptr(out["keep"]), ptr(out["lo"]), ptr(out["hi"]), _stream())
+        return out
+
+    def proof_stats(self):
+        """Counts of proof-guided play so far (sync; spmcts_get_proof_stats): plies chosen with it on, those with a
+        solved root, with a secured win, with fewer kept moves than legal ones (restricted); trees_stopped and
+        sims_skipped of proof_stop."""
+        out = (ctypes.c_int64 * len(self.PROOF_STATS))()
+        call("spmcts_get_proof_stats", self.h, out)
+        return dict(zip(self.PROOF_STATS, (int(x) for x in out)))
+
+    def proof_stop(self):
+        """Between two simulation steps of a threaded search: every searching tree with proof play on whose root
+        is now solved starts no more sims (spmcts_proof_stop).  Queued on the current stream, no host sync."""
+        call("spmcts_proof_stop", self.h, _stream())
+
+    def proof_stopped(self):
+        """Per tree, device int32 [T]: the searches of the tree that proof_stop has stopped so far (no host sync)."""
+        out = torch.empty(self.n_trees, dtype=torch.int32, device=self.device)
+        call("spmcts_proof_stopped", self.h, ptr(out), _stream())
+        return out
+
     # ------------------------------------------------------------------ games API
     def games_set_openings(self, openings, id_period=0):
         """The arena's opening book (include/spmcts.h spmcts_games_set_openings): `openings` a list of move

@@ -382,6 +382,19 @@ __device__ PlayOut play_move_choice(const View &v, int tree, double temp, float 
   const double inv = 1.0 / t;
   double pp[G::A];
   for (int j = 0; j < G::A; ++j) pp[j] = inv == 1.0 ? (double)n[j] : pow((double)n[j], inv);
+  // proof-guided play (arena_proof.h): the moves the tree's own proof keeps, written by k_proof_verdict before
+  // this kernel.  A move outside them weighs nothing; if no kept move has a visit (a win is classified from the
+  // board alone), the kept moves weigh the same.  PF_ALL, the feature off for the tree: nothing here runs
+  const uint32_t keep = v.pf_keep ? v.pf_keep[tree] : PF_ALL;
+  if (keep != PF_ALL) {
+    double ks = 0.0;
+    for (int j = 0; j < G::A; ++j) {
+      if (!((keep >> j) & 1u)) pp[j] = 0.0;
+      ks = ks + pp[j];
+    }
+    if (ks == 0.0)
+      for (int j = 0; j < G::A; ++j) pp[j] = ((keep >> j) & 1u) ? 1.0 : 0.0;
+  }
   double s = 0.0;
   for (int j = 0; j < G::A; ++j) s = s + pp[j];
   double pr[G::A];
@@ -424,9 +437,9 @@ __device__ PlayOut play_move_choice(const View &v, int tree, double temp, float 
     }
     o.qf64 = nd_f<P>(v, nb + root);
   } else {
-    int best = 0;
+    int best = keep == PF_ALL ? 0 : __ffs((int)keep) - 1;  // (over the kept moves; PF_ALL keeps every j)
     for (int j = 1; j < G::A; ++j)
-      if (n[j] > n[best]) best = j;
+      if (((keep >> j) & 1u) && n[j] > n[best]) best = j;
     o.action = best;
   }
   v.noise_on[tree] = 0;  // remove_noise (mcts.py:55-57)

@@ -320,7 +320,7 @@ __device__ __forceinline__ void bounds_enter(const View &v, size_t nb, Board b, 
   dm = group_ballot<P>(desc);
 }
 
-// What each listed tree proves about the exact score s of its root position (solve.h's s: e if a move wins, 0 if
+// What a tree proves about the exact score s of its root position (solve.h's s: e if a move wins, 0 if
 // it fills the board, else -s(child), maximised over the legal moves): lo <= s <= hi, by a minimax over the stored
 // tree with every unexpanded node open.  Depth-first and iterative: the node in hand lives in registers (the same
 // values in every lane of the group), its ancestors in the block's LDS, one frame of three 8-byte words per level,
@@ -328,35 +328,34 @@ __device__ __forceinline__ void bounds_enter(const View &v, size_t nb, Board b, 
 // to the same addresses and reads back what it wrote itself, so no lane waits for another.  A round leaves the node
 // in hand for its parent or descends into its next expanded child: each expanded node is entered once and left
 // once, at most 2 * cap rounds in a sound store.  A walk that is not over by then has met a store that is no tree:
-// SPMCTS_ERR_STATE, and its row is left untouched.
+// it returns false (the caller raises SPMCTS_ERR_STATE and leaves its row untouched).
+// The one walk of k_tree_bounds and of arena_proof.h's kernels.  s_stk: the calling kernel's LDS stack, TB_LEVELS
+// frames for each of its GPB = TB_THREADS / APAD groups; grp: the group's index in the block.  rmlo / rmhi: the
+// root's move of this lane (TB_NONE: illegal); lo / hi: the root's bounds; e0: its empty cells; nodes: the expanded
+// nodes entered.
 template <class G>
-__global__ __launch_bounds__(TB_THREADS) void k_tree_bounds(View v, const int32_t *trees, int n, TreeBoundsOut o) {
-  constexpr int P = G::APAD, GPB = TB_THREADS / P, LEVELS = G::CELLS + 1;
-  __shared__ uint64_t s_stk[LEVELS][3][GPB];
-  const int t = blockIdx.x * TB_THREADS + threadIdx.x;
-  const int i = t / P, lane = t % P, grp = threadIdx.x / P;
-  if (i >= n) return;
-  const int tree = trees[i];
-  if (tree < 0 || tree >= v.T) {
-    if (lane == 0) set_err(v, SPMCTS_ERR_STATE);
-    return;
-  }
+struct TbGrid {
+  static constexpr int GPB = TB_THREADS / G::APAD, LEVELS = G::CELLS + 1;
+  typedef uint64_t Stack[LEVELS][3][GPB];
+};
+
+template <class G>
+__device__ __forceinline__ bool bounds_walk(const View &v, int tree, int lane, int grp,
+                                            typename TbGrid<G>::Stack &s_stk, int &rmlo, int &rmhi, int &lo, int &hi,
+                                            int &e0, int &nodes) {
+  constexpr int P = G::APAD, LEVELS = TbGrid<G>::LEVELS;
   const size_t nb = nbase<G>(v, tree);
   const int rplayer = v.rplayer[tree];
   Board b{v.rpos[tree], v.rneg[tree]};
-  const int e0 = G::CELLS - popc(b.pos | b.neg);
+  e0 = G::CELLS - popc(b.pos | b.neg);
   int cb = nd_c<P>(v, nb + v.root[tree]);
-  int sp = 0, nodes = tree_block_ok(v, cb) ? 1 : 0, root_a = -1;
-  int rmlo, rmhi, lo, hi;  // rmlo / rmhi: the root's move of this lane
+  int sp = 0, root_a = -1;
+  nodes = tree_block_ok(v, cb) ? 1 : 0;
   uint32_t dm;
   bounds_enter<G>(v, nb, b, rplayer, cb, lane, true, rmlo, rmhi, lo, hi, dm);
-  bool over = false;
   for (int it = 0; it <= 2 * v.cap; ++it) {
     if (dm == 0) {  // the node in hand is done: its bounds go to its parent, negated
-      if (sp == 0) {
-        over = true;
-        break;
-      }
+      if (sp == 0) return true;
       const int clo = lo, chi = hi;
       --sp;
       const uint64_t w = s_stk[sp][2][grp];
@@ -384,6 +383,24 @@ __global__ __launch_bounds__(TB_THREADS) void k_tree_bounds(View v, const int32_
       bounds_enter<G>(v, nb, b, (sp & 1) ? -rplayer : rplayer, cb, lane, sp + 1 < LEVELS, mlo, mhi, lo, hi, dm);
     }
   }
+  return false;
+}
+
+// spmcts_tree_bounds_batch: the walk above for each listed tree, one APAD-lane group per tree.
+template <class G>
+__global__ __launch_bounds__(TB_THREADS) void k_tree_bounds(View v, const int32_t *trees, int n, TreeBoundsOut o) {
+  constexpr int P = G::APAD;
+  __shared__ typename TbGrid<G>::Stack s_stk;
+  const int t = blockIdx.x * TB_THREADS + threadIdx.x;
+  const int i = t / P, lane = t % P, grp = threadIdx.x / P;
+  if (i >= n) return;
+  const int tree = trees[i];
+  if (tree < 0 || tree >= v.T) {
+    if (lane == 0) set_err(v, SPMCTS_ERR_STATE);
+    return;
+  }
+  int rmlo, rmhi, lo, hi, e0, nodes;
+  const bool over = bounds_walk<G>(v, tree, lane, grp, s_stk, rmlo, rmhi, lo, hi, e0, nodes);
   if (!over) {
     if (lane == 0) set_err(v, SPMCTS_ERR_STATE);
     return;

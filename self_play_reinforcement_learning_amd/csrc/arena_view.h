@@ -141,7 +141,22 @@ struct View {
   int32_t *lr_plies;
   int32_t *lr_open;   // the game's opening, -1 without a book
   uint8_t *lr_moves;  // [lr_cap][cells], bytes past plies zero
+  // proof-guided play (spmcts_set_proof_play, arena_proof.h; null until it is switched on, pf_keep the one pointer
+  // the move choice tests): pf_on uint8 [T], the trees it is on for; the verdict k_proof_verdict wrote before the
+  // tree's last move choice: pf_keep uint32 [T], the moves the choice may take (PF_ALL: no restriction), pf_lo /
+  // pf_hi int8 [T], the root's score bounds (TB_NONE beside PF_ALL); pf_stats [PF_NSTAT], the PF_* counts below;
+  // pf_nstop int32 [T], the searches of the tree that k_proof_stop has stopped so far
+  uint8_t *pf_on;
+  uint32_t *pf_keep;
+  int8_t *pf_lo, *pf_hi;
+  unsigned long long *pf_stats;
+  int32_t *pf_nstop;
 };
+
+enum : uint32_t { PF_ALL = 0xffffffffu };
+// View::pf_stats: plies chosen with proof play on, those with a solved root (lo == hi), with a secured win
+// (lo > 0), with fewer kept moves than legal ones; trees k_proof_stop stopped, the sims they did not start
+enum { PF_PLIES = 0, PF_SOLVED = 1, PF_WON = 2, PF_CUT = 3, PF_STOPPED = 4, PF_SKIPPED = 5, PF_NSTAT = 6 };
 
 enum { BOOK_MAX_OPENINGS = 65536 };
 

@@ -36,6 +36,7 @@
 //   arena_games.h   game state machine (opening book plies included), the hard-coded players, k_root_stats_batch, export
 //   arena_tree.h    reading the trees below the root: k_tree_pv (principal variations), k_tree_export (subtrees),
 //                   k_tree_bounds (what a tree proves: bounds on the exact score)
+//   arena_proof.h   playing what a tree has proved: k_proof_verdict (the moves the move choice may take), k_proof_stop
 //   records.h       game records (move lists) to the positions before their moves: spmcts_log_positions and its host twin
 //   arena_misc.h    k_env_step, k_table_net, k_copy_probe, the init kernels
 //   arena_league.h  league routing: a step's rows partitioned by their tree's network, and back
@@ -96,6 +97,7 @@ static int fail(int code, const std::string &msg) {
 #include "solve.h"
 #include "arena_games.h"
 #include "arena_tree.h"
+#include "arena_proof.h"
 #include "records.h"
 #include "arena_misc.h"
 #include "arena_league.h"
@@ -145,6 +147,9 @@ struct spmcts_arena {
   // off (View::glog null), and the log's address for turning it on again
   std::vector<void *> log_allocs;
   uint8_t *log_dev = nullptr;
+  // proof-guided play (spmcts_set_proof_play): the View::pf_* arrays' allocations (flags, keep, lo, hi, stats, stop
+  // counts), kept while the feature is off for every tree (View::pf_keep null)
+  std::vector<void *> proof_allocs;
 };
 
 static bool league_on(const spmcts_arena *h) { return h->lg.n > 0; }
@@ -505,6 +510,7 @@ int spmcts_arena_destroy(spmcts_arena *h) {
   for (void *p : h->league_allocs) (void)hipFree(p);
   if (h->nm_alloc) (void)hipFree(h->nm_alloc);
   for (void *p : h->log_allocs) (void)hipFree(p);
+  for (void *p : h->proof_allocs) (void)hipFree(p);
   delete h;
   return 0;
 }
@@ -957,6 +963,9 @@ int spmcts_search_end(spmcts_arena *h, double temp, int32_t *actions_dev, int8_t
   if (!h) return fail(-1, "null arena");
   const int n = h->n_active;
   if (n <= 0) return 0;
+  if (h->v.pf_keep)  // the active trees' verdicts, read by k_search_end
+    TRY(LAUNCH(h, k_proof_verdict, (long long)n * h->P, TB_THREADS, (hipStream_t)stream, h->v, (const int32_t *)nullptr,
+               n, (int)PF_MODE_ACTIVE, h->v.pf_keep, h->v.pf_lo, h->v.pf_hi));
   return LAUNCH(h, k_search_end, n, 64, (hipStream_t)stream, h->v, n, temp, actions_dev, states_dev, tree_probs_dev,
                 q_dev, q_f64_dev, recorded_dev);
 }
@@ -1047,6 +1056,9 @@ int spmcts_games_end_ply(spmcts_arena *h, void *leaves_dev, int32_t *leaf_count_
   if (!h) return fail(-1, "null arena");
   hipStream_t s = (hipStream_t)stream;
   if (h->nm_on) TRY(negamax_games(h, s));  // the negamax movers' codes, read by k_games_end_ply
+  if (h->v.pf_keep)  // the mover trees' verdicts, read by k_games_end_ply
+    TRY(LAUNCH(h, k_proof_verdict, (long long)h->v.G * h->P, TB_THREADS, s, h->v, (const int32_t *)nullptr, h->v.G,
+               (int)PF_MODE_GAMES, h->v.pf_keep, h->v.pf_lo, h->v.pf_hi));
   TRY(LAUNCH(h, k_games_end_ply, h->v.G, 64, s, h->v));
   return launch_rows(h, leaves_dev, leaf_count_dev, s, false);
 }
@@ -1242,6 +1254,97 @@ int spmcts_tree_bounds_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t 
   if (!trees_dev) return fail(-1, "null argument");
   const TreeBoundsOut o{lo_dev, hi_dev, move_lo_dev, move_hi_dev, best_dev, empty_dev, nodes_dev};
   return LAUNCH(h, k_tree_bounds, (long long)n * h->P, TB_THREADS, (hipStream_t)stream, h->v, trees_dev, n, o);
+}
+
+// ---- proof-guided play -------------------------------------------------------
+int spmcts_set_proof_play(spmcts_arena *h, const uint8_t *on) {
+  if (!h) return fail(-1, "null arena");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t T = h->v.T;
+  std::vector<uint8_t> f(T, 1);
+  bool any = !on;
+  if (on)
+    for (size_t t = 0; t < T; ++t) any |= (f[t] = on[t] ? 1 : 0) != 0;
+  View &v = h->v;
+  if (!any && h->proof_allocs.empty()) return 0;  // never on: nothing to switch off
+  const size_t bytes[6] = {T, 4 * T, T, T, 8 * PF_NSTAT, 4 * T};
+  if (h->proof_allocs.empty()) {
+    void *p[6] = {};
+    for (int i = 0; i < 6; ++i) {
+      hipError_t e = hipMalloc(&p[i], bytes[i]);
+      if (e == hipSuccess) e = hipMemset(p[i], 0, bytes[i]);
+      if (e != hipSuccess) {
+        for (int j = 0; j <= i; ++j)
+          if (p[j]) (void)hipFree(p[j]);
+        return fail(-1000 - (int)e, std::string("proof play hipMalloc: ") + hipGetErrorString(e));
+      }
+    }
+    h->proof_allocs.assign(p, p + 6);
+  }
+  void *const *p = h->proof_allocs.data();
+  HIP_TRY(hipMemcpy(p[0], f.data(), T, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(p[1], 0xff, bytes[1]));  // PF_ALL: no verdict yet
+  HIP_TRY(hipMemset(p[2], 0x80, bytes[2]));  // TB_NONE
+  HIP_TRY(hipMemset(p[3], 0x80, bytes[3]));
+  HIP_TRY(hipDeviceSynchronize());
+  v.pf_on = any ? (uint8_t *)p[0] : nullptr;
+  v.pf_keep = any ? (uint32_t *)p[1] : nullptr;
+  v.pf_lo = any ? (int8_t *)p[2] : nullptr;
+  v.pf_hi = any ? (int8_t *)p[3] : nullptr;
+  v.pf_stats = any ? (unsigned long long *)p[4] : nullptr;
+  v.pf_nstop = any ? (int32_t *)p[5] : nullptr;
+  return 0;
+}
+
+int spmcts_tree_proof_moves_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n, uint32_t *keep_dev,
+                                  int8_t *lo_dev, int8_t *hi_dev, spmcts_stream stream) {
+  if (!h) return fail(-1, "null arena");
+  if (n < 0) return fail(-3, "tree_proof_moves: n must not be negative");
+  if (n == 0) return 0;
+  if (!trees_dev) return fail(-1, "null argument");
+  return LAUNCH(h, k_proof_verdict, (long long)n * h->P, TB_THREADS, (hipStream_t)stream, h->v, trees_dev, n,
+                (int)PF_MODE_LIST, keep_dev, lo_dev, hi_dev);
+}
+
+int spmcts_proof_last(spmcts_arena *h, uint32_t *keep_dev, int8_t *lo_dev, int8_t *hi_dev, spmcts_stream stream) {
+  if (!h) return fail(-1, "null arena");
+  if (!h->v.pf_keep) return fail(-4, "proof play is off (spmcts_set_proof_play)");
+  const size_t T = h->v.T;
+  hipStream_t s = (hipStream_t)stream;
+  if (keep_dev) HIP_TRY(hipMemcpyAsync(keep_dev, h->v.pf_keep, 4 * T, hipMemcpyDeviceToDevice, s));
+  if (lo_dev) HIP_TRY(hipMemcpyAsync(lo_dev, h->v.pf_lo, T, hipMemcpyDeviceToDevice, s));
+  if (hi_dev) HIP_TRY(hipMemcpyAsync(hi_dev, h->v.pf_hi, T, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+int spmcts_get_proof_stats(spmcts_arena *h, int64_t *out) {
+  if (!h || !out) return fail(-1, "null argument");
+  for (int i = 0; i < SPMCTS_PROOF_NSTAT; ++i) out[i] = 0;
+  if (h->proof_allocs.empty()) return 0;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  static_assert(SPMCTS_PROOF_NSTAT == PF_NSTAT, "proof stats layout");
+  HIP_TRY(hipMemcpy(out, h->proof_allocs[4], 8 * PF_NSTAT, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int spmcts_proof_stopped(spmcts_arena *h, int32_t *count_dev, spmcts_stream stream) {
+  if (!h || !count_dev) return fail(-1, "null argument");
+  const size_t T = h->v.T;
+  if (h->proof_allocs.empty()) {
+    HIP_TRY(hipMemsetAsync(count_dev, 0, 4 * T, (hipStream_t)stream));
+  } else {
+    HIP_TRY(hipMemcpyAsync(count_dev, h->proof_allocs[5], 4 * T, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  }
+  return 0;
+}
+
+int spmcts_proof_stop(spmcts_arena *h, spmcts_stream stream) {
+  if (!h) return fail(-1, "null arena");
+  if (h->v.K <= 1) return fail(-4, "proof_stop needs search_threads > 1 (a sequential search has no sims left to skip)");
+  if (!h->v.pf_keep) return fail(-4, "proof_stop needs proof play (spmcts_set_proof_play)");
+  return LAUNCH(h, k_proof_stop, (long long)h->v.T * h->P, TB_THREADS, (hipStream_t)stream, h->v);
 }
 
 // ---- league ---------------------------------------------------------------

@@ -311,7 +311,7 @@ class Elo:
                 kw = e["policy_kwargs"]
                 out.append(dict(network=self.model_database.network(name), iterations=int(kw.get("iterations", 100)),
                                 alpha=float(kw.get("alpha", 1)), strong_play=bool(kw.get("strong_play", False)),
-                                search_threads=self.search_threads))
+                                search_threads=self.search_threads, proof_play=bool(kw.get("proof_play", False))))
             elif e["policy"] == "Negamax":
                 out.append(dict(kind="negamax", depth=int(e["policy_kwargs"].get("depth", 2))))
             else:
@@ -413,17 +413,19 @@ class Elo:
             out("")
         return records
 
-    def analyse(self, name, moves, pv_len=8, tree_depth=2, min_visits=2, out=None, bounds=False):
+    def analyse(self, name, moves, pv_len=8, tree_depth=2, min_visits=2, out=None, bounds=False, kept_moves=False):
         """One registered MCTreeSearch model's search of the position after `moves` (a move list from the empty
         board): mcts.analyse_positions with the model's own iterations / alpha / strong_play, its principal
         variation of at most pv_len moves and its tree to tree_depth (nodes with at least min_visits visits).
         Returns analyse_positions' dict for the one position plus "view" (the tree.TreeView) and "text" (the root
         table, the PV and the rendered tree); out (e.g. print) receives the text.  bounds=True adds what the
         search's tree has proved about the position (Arena.bounds_batch; analyse_positions' bound_* keys) and one
-        more line of text, e.g. "proved: win in 5 by 3" or "bounds: at least a draw" (tree.describe_bounds)."""
+        more line of text, e.g. "proved: win in 5 by 3" or "bounds: at least a draw" (tree.describe_bounds).
+        kept_moves=True (with bounds) appends the moves proof-guided play would choose among to that line,
+        "proved: win in 5 by 3; keeps 3" (analyse_positions' keep; tree.describe_proof_moves)."""
         from .arena import game_of_env
         from .mcts import analyse_positions
-        from .tree import TreeView, describe_bounds
+        from .tree import TreeView, describe_bounds, describe_proof_moves
 
         entry = self.model_database.models()[name]
         if entry["policy"] != "MCTreeSearch":
@@ -456,6 +458,8 @@ class Elo:
             empty = int((res["board"][0] == 0).sum())
             lines.append(describe_bounds(int(res["bound_lo"][0]), int(res["bound_hi"][0]), empty,
                                          int(res["bound_best"][0])))
+            if kept_moves:
+                lines[-1] += "; " + describe_proof_moves(int(res["keep"][0]) & 0xffffffff)
         res = dict(res, view=view, text="\n".join(lines))
         if out is not None:
             out(res["text"])
@@ -514,6 +518,8 @@ def main(argv=None):
     parser.add_argument("--min-visits", type=int, default=2, help="analyse: fewest visits of a node shown")
     parser.add_argument("--bounds", action="store_true",
                         help="analyse: add what the search's tree has proved about the position")
+    parser.add_argument("--kept-moves", action="store_true",
+                        help="analyse --bounds: add the moves proof-guided play would choose among to that line")
     args = parser.parse_args(argv)
     env = {"connect4": Connect4Env, "tictactoe": TicTacToeEnv}[args.game](*[int(x) for x in args.board_size or []])
     elo = Elo(ModelDatabase(args.dir, env))
@@ -529,7 +535,7 @@ def main(argv=None):
         if not args.p or len(args.p) != 1:
             parser.error("analyse needs --p with one model name")
         elo.analyse(args.p[0], args.moves, pv_len=args.pv, tree_depth=args.tree_depth, min_visits=args.min_visits,
-                    out=print, bounds=args.bounds)
+                    out=print, bounds=args.bounds, kept_moves=args.kept_moves)
     else:
         names = args.p or list(elo.model_database.models().keys())
         print(json.dumps(elo.compare_models(*names, num_games=args.games, openings=args.openings,

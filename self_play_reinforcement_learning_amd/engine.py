@@ -102,8 +102,14 @@ class SelfPlayEngine:
                  leaf_layout="nhwc", cpuct=4.0, x_noise=0.25, blocks_per_tree=0, bucket=256, opponent=None,
                  opponent_iterations=None, record=True, search_threads=1, leaf_dedup=None, opponent_alpha=None,
                  opponent_strong_play=None, opponent_search_threads=None, eval_cache=None, openings=None,
-                 opening_period=0, opponent_depth=2, record_games=False):
-        """record_games: keep every finished game's move list (the arena's game log, include/spmcts.h
+                 opening_period=0, opponent_depth=2, record_games=False, proof_play=False, opponent_proof_play=None,
+                 proof_stop_every=0):
+        """proof_play: the policy's move choice uses what its tree has proved (Arena.set_proof_play; off by
+        default); opponent_proof_play: the same for the opposing MCTS side, None = the policy's (a hard-coded
+        opponent is unaffected either way).  proof_stop_every=N > 0: after every N-th simulation step of a ply a
+        searching tree whose root is solved starts no more sims (Arena.proof_stop, queued on the engine's stream
+        without a host sync); needs proof_play and search_threads > 1; 0 = off.
+        record_games: keep every finished game's move list (the arena's game log, include/spmcts.h
         spmcts_games_set_log; drained once per ply next to the Move export): game_records() returns them.
         opponent_depth: the horizon of opponent="negamax" (hardcoded_players.Negamax; 1 .. 6 on the device).
         openings: an opening book, a list of move lists from the empty board (openings.py; include/spmcts.h
@@ -185,6 +191,20 @@ class SelfPlayEngine:
             raise ValueError("eval_cache needs leaf dedup (pure evaluators, search_threads > 1)")
         if self.eval_cache:
             self.arena.set_eval_cache(self.eval_cache)
+        # proof-guided play (include/spmcts.h spmcts_set_proof_play): tree 2g = the policy, 2g + 1 = the opposing player
+        pp0 = bool(proof_play)
+        pp1 = pp0 if opponent_proof_play is None else bool(opponent_proof_play)
+        self.proof_play = pp0 or pp1
+        self.proof_stop_every = int(proof_stop_every or 0)
+        self._sim_step = 0  # the simulation step in hand (_ply_sim_net), for _proof_stop_after
+        if self.proof_stop_every < 0:
+            raise ValueError("proof_stop_every must be 0 (off) or a positive number of simulation steps")
+        if self.proof_stop_every and not self.proof_play:
+            raise ValueError("proof_stop_every needs proof_play=True")
+        if self.proof_stop_every and self.search_threads < 2:
+            raise ValueError("proof_stop_every needs search_threads > 1")
+        if self.proof_play:
+            self.arena.set_proof_play([pp0, pp1] * n_games)
         self.openings = None
         if openings:
             self.openings = validate_openings(game, openings)
@@ -337,6 +357,15 @@ class SelfPlayEngine:
             a.expand2(probs, values, p1, v1)
         if self.expand_timer is not None:
             self.expand_timer.stop()
+        if sim:
+            self._proof_stop_after(self._sim_step)
+
+    def _proof_stop_after(self, step):
+        """proof_stop_every: after simulation step `step` of the ply (0-based), if it is an N-th one and not the
+        last (after the last no tree has a sim left to start)."""
+        n = self.proof_stop_every
+        if n and (step + 1) % n == 0 and step + 1 < self.select_steps:
+            self.arena.proof_stop()
 
     # --- one ply in phases (LanedEngine interleaves the phases of several engines on their streams)
     def _ply_begin(self):
@@ -354,6 +383,7 @@ class SelfPlayEngine:
 
     def _ply_sim_net(self, step=0):
         """The rows and network half of _ply_simulation."""
+        self._sim_step = step
         if step == 0 or self.search_threads == 1:
             self.arena.select_async(self.select_timer)
         else:
@@ -374,8 +404,9 @@ class SelfPlayEngine:
                 self._ply_simulation(i)
             self._ply_move()
         else:
-            for _ in range(self.select_steps):
+            for i in range(self.select_steps):
                 self._eval_expand(a.select(self.select_timer))
+                self._proof_stop_after(i)
             self._eval_expand(a.games_end_ply())
         return self._ply_finish(on_moves, refill, game_offset)
 
@@ -552,7 +583,8 @@ class LanedEngine:
     def __init__(self, game, network, n_games=4096, lanes=2, seed=0, subsequence0=None, device=None, pack=True,
                  stagger=False, cross_dedup=None, lane_sizes=None, **kw):
         # openings= / opening_period= (SelfPlayEngine): every lane gets the same book and assigns it by its
-        # lane-local game ids
+        # lane-local game ids; proof_play= / opponent_proof_play= / proof_stop_every= reach every lane too (a lane's
+        # proof_stop is queued on its own stream, after the expand of the step)
         if lanes < 1 or n_games < lanes:
             raise ValueError(f"need 1 <= lanes <= n_games (lanes={lanes}, n_games={n_games})")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -884,8 +916,12 @@ class LeagueEngine:
 
     def __init__(self, game, players, pairings, games_per_pairing=100, seed=0, search_threads=4,
                  dtype=torch.float16, subsequence0=0, device=None, leaf_layout="nhwc", cpuct=4.0, x_noise=0.25,
-                 blocks_per_tree=0, openings=None, rng="philox", record_games=False):
-        """record_games: keep every game's move list (the arena's game log, drained once per ply); game_records()
+                 blocks_per_tree=0, openings=None, rng="philox", record_games=False, proof_stop_every=0):
+        """A player dict's "proof_play": True switches proof-guided play on for that player's trees (Arena.
+        set_proof_play; per player, so one net can meet itself with and without it; a hard-coded player ignores it).
+        proof_stop_every=N > 0: after every N-th simulation step of a ply a searching tree with proof play whose root
+        is solved starts no more sims (Arena.proof_stop); needs a proof_play player and search_threads > 1.
+        record_games: keep every game's move list (the arena's game log, drained once per ply); game_records()
         returns them with each record's pairing and its two players' names (a player dict's "name", else its index).
         rng: "philox", or "tape" (every tree draws from its own given stream: Arena.set_tapes before start()).
         openings: an opening book (openings.py) with id period g, the per-pairing slot count: every pairing
@@ -955,6 +991,17 @@ class LeagueEngine:
                           search_threads=[min(a.search_threads, max(1, int(x))) for x in per_tree("search_threads", K0)])
         a.set_tree_players(nets=None, kinds=kinds, budgets=[int(x) for x in per_tree("iterations", 100)])
         a.games_set_record(False)
+        proof = [bool(x) for x in per_tree("proof_play", False)]
+        self.proof_play = any(proof)
+        self.proof_stop_every = int(proof_stop_every or 0)
+        if self.proof_stop_every < 0:
+            raise ValueError("proof_stop_every must be 0 (off) or a positive number of simulation steps")
+        if self.proof_stop_every and not self.proof_play:
+            raise ValueError("proof_stop_every needs a player with proof_play=True")
+        if self.proof_stop_every and self.search_threads < 2:
+            raise ValueError("proof_stop_every needs search_threads > 1")
+        if self.proof_play:
+            a.set_proof_play(proof)
         self.record_games = bool(record_games)
         self._records = None
         if self.record_games:
@@ -1041,6 +1088,9 @@ class LeagueEngine:
             else:
                 a.leaf_rows_async()
             self._eval_expand()
+            n = self.proof_stop_every
+            if n and (step + 1) % n == 0 and step + 1 < self.select_steps:
+                a.proof_stop()
         a.games_end_ply_async()
         self._eval_expand()
         finished, _ = a.games_finish_ply(refill=False)

@@ -72,7 +72,7 @@ class MCTreeSearch(Policy):
     def __init__(self, network=None, env=None, optim=None, memory_queue=None, iterations=100, temperature_cutoff=5,
                  batch_size=64, memory_size=200000, min_memory=20000, update_nn=True, starting_state_dict=None,
                  thread_count=4, strong_play=False, q_average=True, alpha=1, env_gen=None, evaluator=None,
-                 seed=None, device=None, rng="philox", cpuct=4, x_noise=0.25, threading=False):
+                 seed=None, device=None, rng="philox", cpuct=4, x_noise=0.25, threading=False, proof_play=False):
         network = network if network is not None else evaluator
         env = env if env is not None else env_gen
         if network is None or env is None:
@@ -110,6 +110,10 @@ class MCTreeSearch(Policy):
                             strong_play=strong_play, leaf_format=self._evaluator.leaf_format,
                             leaf_layout=self._evaluator.leaf_layout, cpuct=cpuct, x_noise=x_noise, alpha=alpha,
                             device=self.device, search_threads=k)
+        # proof_play=True: the move choice drops the moves the tree's own proof rules out (Arena.set_proof_play)
+        self.proof_play = bool(proof_play)
+        if self.proof_play:
+            self._arena.set_proof_play(True)
         self.temp_memory = []
         self.moves_played = 0
         # weights changed (update_from_memory / load_state_dict): the evaluator's folded / packed copy is
@@ -244,6 +248,15 @@ class MCTreeSearch(Policy):
                    move_hi_code=bounds_to_codes(raw["move_hi"], e).tolist())
         return out
 
+    def proof_moves(self):
+        """What proof-guided play would keep at the active root as the tree stands (Arena.proof_moves_batch; the
+        tree is only read, proof_play on or off): dict(keep: the kept actions, a list; mask: the same as bits; lo,
+        hi: the root's score bounds)."""
+        out = {k: int(v[0]) for k, v in self._arena.proof_moves_batch([0]).items()}
+        self._arena.check()
+        mask = out["keep"] & 0xffffffff
+        return dict(keep=[a for a in range(self.actions) if (mask >> a) & 1], mask=mask, lo=out["lo"], hi=out["hi"])
+
     # ------------------------------------------------------------------ memory / training
     def update(self, s, a, r, done, next_s):
         self.push_to_queue(s, a, r, done, next_s)
@@ -328,7 +341,9 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
     tree=dict(max_nodes=, min_visits=, max_depth=) adds Arena.export_subtrees' arrays of every position under
     "tree" (tree.TreeView.from_export(out["tree"], i) for position i).  bounds=True adds what each position's tree
     has proved (Arena.bounds_batch): bound_lo, bound_hi int8 [n] (lo <= s <= hi for the exact solver's score s),
-    move_lo, move_hi int8 [n, A], bound_best int8 [n], bound_nodes int32 [n].  None of them changes the other keys."""
+    move_lo, move_hi int8 [n, A], bound_best int8 [n], bound_nodes int32 [n], and keep int32 [n], the moves
+    proof-guided play would choose among (Arena.proof_moves_batch; bit a: move a).  None of them changes the other
+    keys."""
     from .openings import validate_openings
 
     game = game if isinstance(game, str) else game_of_env(game)
@@ -370,7 +385,7 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
         if bounds:
             b = arena.bounds_batch(trees)
             out.update(bound_lo=b["lo"], bound_hi=b["hi"], move_lo=b["move_lo"], move_hi=b["move_hi"],
-                       bound_best=b["best"], bound_nodes=b["nodes"])
+                       bound_best=b["best"], bound_nodes=b["nodes"], keep=arena.proof_moves_batch(trees)["keep"])
         arena.check()
     finally:
         arena.close()

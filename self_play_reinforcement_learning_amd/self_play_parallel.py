@@ -194,7 +194,7 @@ class SelfPlayScheduler:
         threads = self._resolve_threads(inference_proxy)
         ekw = dict(iterations=kw.get("iterations", 100), alpha=kw.get("alpha", 1),
                    strong_play=kw.get("strong_play", False), seed=self.seed + 7919 * self.rank, device=self.device,
-                   search_threads=max(1, threads))
+                   search_threads=max(1, threads), proof_play=bool(kw.get("proof_play", False)))
         lanes = self.lanes if self.lanes is not None else (2 if n_games >= 1024 else 1)
         if lanes > 1 and n_games >= 2 * lanes:
             self.engine = LanedEngine(self.game, self.network, n_games=n_games, lanes=lanes, **ekw)
@@ -424,13 +424,17 @@ class SelfPlayScheduler:
     def _evaluation_engine(self, n_games, openings=None):
         opponent, opp_kw = self._opponent()
         kw = self._policy_kwargs()
+        # proof-guided play is each side's own setting too (its container's proof_play; hard-coded players ignore it)
+        okw = getattr(self.evaluation_policy_container, "policy_kwargs", None) or {}
         per_rank = max(1, n_games // self.world + (1 if self.rank < n_games % self.world else 0))
         slots = min(per_rank, self.n_games or 4096)
         self.network.eval()
         return SelfPlayEngine(self.game, self.network, n_games=slots, iterations=kw.get("iterations", 100),
                               alpha=kw.get("alpha", 1), strong_play=kw.get("strong_play", False), evaluate=True,
                               seed=self.seed + 104729 + 7919 * self.rank, device=self.device, opponent=opponent,
-                              record=False, search_threads=self._search_threads, openings=openings, **opp_kw), per_rank
+                              record=False, search_threads=self._search_threads, openings=openings,
+                              proof_play=bool(kw.get("proof_play", False)),
+                              opponent_proof_play=bool(okw.get("proof_play", False)), **opp_kw), per_rank
 
     def _play_evaluation(self, n_games, openings=None, records=None):
         """n_games evaluation games over all ranks (task i -> swap_sides = i odd, update=False);

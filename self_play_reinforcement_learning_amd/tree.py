@@ -62,6 +62,28 @@ def describe_bounds(lo, hi, empty, best):
     return {"not_lost": "bounds: at least a draw", "not_won": "bounds: at most a draw", "open": "bounds: open"}[status]
 
 
+def proof_move_set(lo, hi, move_lo, move_hi):
+    """The keep set of proof-guided play (include/spmcts.h spmcts_set_proof_play; the host twin of
+    Arena.proof_moves_batch's keep) from a root's score bounds (Arena.bounds_batch): bit a of the mask is set iff
+    move a is legal (move_lo[a] != -128) and move_lo[a] == lo where lo > 0 (a win is secured) or lo == hi (the root
+    is solved), move_hi[a] >= lo otherwise (a move proved worse than what another already secures is dropped).
+    Never empty for a root with a legal move.  lo, hi: ints or [n]; move_lo, move_hi: [A] or [n, A] (lists, numpy
+    arrays or tensors); an int for one root, else a numpy int64 array [n]."""
+    arr = lambda x: np.asarray(x.cpu() if hasattr(x, "cpu") else x).astype(np.int64)  # noqa: E731
+    lo, hi, mlo, mhi = arr(lo), arr(hi), arr(move_lo), arr(move_hi)
+    scalar = lo.ndim == 0
+    lo, hi = lo.reshape(-1, 1), hi.reshape(-1, 1)
+    mlo, mhi = mlo.reshape(lo.shape[0], -1), mhi.reshape(lo.shape[0], -1)
+    keep = (mlo != BOUND_ILLEGAL) & np.where((lo > 0) | (lo == hi), mlo == lo, mhi >= lo)
+    mask = (keep.astype(np.int64) << np.arange(keep.shape[1], dtype=np.int64)).sum(axis=1)
+    return int(mask[0]) if scalar else mask
+
+
+def describe_proof_moves(keep):
+    """The kept moves of a mask as text: "keeps 2 3" (proof_move_set's mask; Arena.proof_moves_batch's keep)."""
+    return "keeps " + " ".join(str(a) for a in range(32) if (int(keep) >> a) & 1)
+
+
 def _env_of(game):
     from .arena import GAMES
     from .envs import Connect4Env, TicTacToeEnv
