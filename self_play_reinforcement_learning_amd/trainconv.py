@@ -11,7 +11,8 @@ module's own nn.Conv2d.forward runs again.
 Numerics: fp16 operands, fp32 accumulation, one rounding to fp16 per output (as MIOpen's fp16
 kernels); the weight gradient is summed over board groups in a fixed order, so results are
 deterministic.  Checked against the fp32 torch convolution of the same fp16 operands in
-tests/test_gpu_trainconv.py.
+tests/test_gpu_trainconv.py, and bit for bit against fp64 on integer operands (all four (cin, cout) pairs of
+128 and 256) in tests/test_gpu_exact_kernels.py.
 """
 import contextlib
 import ctypes
