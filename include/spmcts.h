@@ -358,6 +358,44 @@ int spmcts_proof_stop(spmcts_arena *h, spmcts_stream stream);
  * queued on the stream with no host synchronisation; all 0 where proof play was never on. */
 int spmcts_proof_stopped(spmcts_arena *h, int32_t *count_dev, spmcts_stream stream);
 
+/* ---- stored score bounds ---------------------------------------------------- */
+/* Solver-aware search (off by default).  `on` uint8 [T]: the trees whose search uses the stored bounds, or NULL:
+ * every tree.  The first call starts the maintenance of the bounds for the whole arena (it cannot be switched off
+ * again); later calls may change the use flags between launches.  THIS VERSION BUILDS THE MAINTENANCE ONLY: the
+ * search rules that read the bounds during a descent are not built, so a call with any flag set (NULL included)
+ * returns -2 and changes nothing, and a call with every flag 0 is how the bounds are switched on.  From that call on every
+ * entry j of every child block carries move_lo / move_hi of the move into child j as int8, seen from the block's
+ * own node -- the values the walk of spmcts_tree_bounds_batch computes for that move -- in bytes of the node record
+ * that were padding, so no layout, size or offset changes.  A new block is stamped from its board alone (a winning
+ * move [e, e], a board-filling move [0, 0], an illegal move -128, any other move [-(e - 1), e - 2]); the expansion
+ * that created it then rewrites the leaf's entry in its parent's block as [-hi, -lo] of the new block and goes on
+ * bottom-up along the expansion's path while an entry changes, up to the entries of the active root's children.
+ * Between any two launches, mid-search included, the stored entries of every block reachable from the active root
+ * equal the walk's values on the tree as it stands.  The search itself does not read them: counters, visit counts,
+ * Move records and results are bit-identical with and without.  With the bounds stored, spmcts_set_proof_play's
+ * verdict before a move choice, spmcts_tree_proof_moves_batch and spmcts_proof_stop read the root's block (one
+ * read) and walk nothing; a root without a child block is classified from its board as before.
+ * spmcts_tree_bounds_batch keeps walking: it is the independent check.
+ * The first call is legal only while no tree holds more than its root block (before the first search): -4
+ * otherwise.  It stamps every fresh tree's root block.  Every call synchronises.  -1: null handle; -2: a use flag
+ * is set. */
+int spmcts_set_solver_search(spmcts_arena *h, const uint8_t *on);
+/* Where each tree's search stands, queued on the stream with no host synchronisation, int32 [T] each, either may be
+ * NULL: started, the search_node calls the tree's current search has started (0x3fffffff: no search in progress,
+ * or stopped by spmcts_proof_stop); resume, the slot its cycle goes on at * 2 + 1 if the sim cap paused it inside a
+ * fill (the state spmcts_proof_stop passes over).  Read-only. */
+int spmcts_search_progress(spmcts_arena *h, int32_t *started_dev, int32_t *resume_dev, spmcts_stream stream);
+/* spmcts_tree_export_batch (the same arguments, the same kernel) with two more outputs, int8 [n][max_nodes] each and
+ * nullable like the others: the stored entry of each exported node, i.e. move_lo / move_hi of the move into it seen
+ * from its parent; -128 in both for the root's row and for an illegal move.  -4: the arena keeps no stored bounds
+ * (spmcts_set_solver_search). */
+int spmcts_tree_export_bounds_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n, int32_t max_nodes,
+                                    int32_t min_visits, int32_t max_depth, int32_t *parent_dev, int8_t *action_dev,
+                                    int16_t *depth_dev, int32_t *node_n_dev, int32_t *node_vl_dev, double *node_w_dev,
+                                    float *node_p_dev, int8_t *player_dev, uint8_t *flags_dev, int32_t *count_dev,
+                                    int8_t *move_lo_dev, int8_t *move_hi_dev, void *work_dev, uint64_t work_bytes,
+                                    spmcts_stream stream);
+
 /* ---- games-level API (SelfPlayer.play_episode state machine) -------------- */
 /* Start games in the listed slots (selfplayworker.py:172-179): both trees reset,
  * swap_sides = game id odd (self_play_parallel.py:237).  Game ids continue from

@@ -21,7 +21,9 @@ the search trees below the root (tree.py: TreeView over Arena.export_subtrees; A
 MCTreeSearch.principal_variation / .tree), and what a search tree has proved about its position (Arena.bounds_batch,
 MCTreeSearch.score_bounds, TreeView.score_bounds; tree.py: bounds_to_codes, classify_bounds, describe_bounds), and
 playing it (proof_play= of MCTreeSearch / SelfPlayEngine / a LeagueEngine player: Arena.set_proof_play,
-proof_moves_batch, proof_last, proof_stats, proof_stop; tree.proof_move_set, the keep set's host twin).
+proof_moves_batch, proof_last, proof_stats, proof_stop; tree.proof_move_set, the keep set's host twin), and keeping
+the bounds in the nodes (stored_bounds= of MCTreeSearch / SelfPlayEngine: Arena.set_stored_bounds,
+Arena.export_subtrees(bounds=True), TreeView.node_bounds).
 """
 from .base_model import BasePlayer, ModelContainer, Policy, TrainableModel  # noqa: F401
 from .memory import Memory  # noqa: F401

@@ -135,6 +135,10 @@ _SIGS = {
     "spmcts_get_proof_stats": [_P, _P],
     "spmcts_proof_stop": [_P, _P],
     "spmcts_proof_stopped": [_P, _P, _P],
+    "spmcts_set_solver_search": [_P, _P],
+    "spmcts_search_progress": [_P, _P, _P, _P],
+    "spmcts_tree_export_bounds_batch": [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                        _P, _U64, _P],
     "spmcts_set_league": [_P, _P, _I32],
     "spmcts_league_segments": [_P, _P],
     "spmcts_league_route": [_P, _P, _P, _I32, _P, _P, _P],

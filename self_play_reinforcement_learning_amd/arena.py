@@ -427,7 +427,9 @@ class Arena:
                      ("node_n", torch.int32, 0), ("node_vl", torch.int32, 0), ("node_w", torch.float64, 0),
                      ("node_p", torch.float32, 0), ("player", torch.int8, 0), ("flags", torch.uint8, 0))
 
-    def export_subtrees(self, trees, max_nodes, min_visits=1, max_depth=None, out=None):
+    EXPORT_BOUND_FIELDS = (("move_lo", torch.int8, -128), ("move_hi", torch.int8, -128))
+
+    def export_subtrees(self, trees, max_nodes, min_visits=1, max_depth=None, out=None, bounds=False):
         """The subtree under the active root of the listed trees in breadth-first order as device tensors, queued
         on the current stream without a host synchronisation (include/spmcts.h spmcts_tree_export_batch).  Row i
         lists tree trees[i]: entry 0 the root, then for each entry in order its children with at least min_visits
@@ -438,14 +440,18 @@ class Arena:
         max_nodes the first max_nodes are there and the call may be repeated with more room (tree.TreeView's
         `truncated`).  out: a dict of the caller's own contiguous device tensors to write into instead of new ones
         (the same keys and dtypes; rows of max_nodes entries from the start of each, so at least n * max_nodes
-        elements; whatever lies past them is not touched)."""
+        elements; whatever lies past them is not touched).  bounds=True (an arena with stored bounds,
+        set_stored_bounds; spmcts_tree_export_bounds_batch): two more columns, move_lo / move_hi int8, each node's
+        stored entry -- the score bounds of the move into it, seen from its parent; -128 for the root, an illegal
+        move and the padding (tree.TreeView.node_bounds recomputes them on the host)."""
         t = trees.to(self.device, torch.int32).contiguous() if torch.is_tensor(trees) else self._dev_i32(trees)
         n, M, dev = int(t.numel()), int(max_nodes), self.device
+        fields = self.EXPORT_FIELDS + (self.EXPORT_BOUND_FIELDS if bounds else ())
         if out is None:
-            out = {k: torch.full((n, M), fill, dtype=dt, device=dev) for k, dt, fill in self.EXPORT_FIELDS}
+            out = {k: torch.full((n, M), fill, dtype=dt, device=dev) for k, dt, fill in fields}
             out["count"] = torch.zeros(n, dtype=torch.int32, device=dev)
         else:
-            for k, dt, _ in self.EXPORT_FIELDS + (("count", torch.int32, 0),):
+            for k, dt, _ in fields + (("count", torch.int32, 0),):
                 need = n if k == "count" else n * max(M, 0)
                 if out[k].dtype != dt or out[k].device != dev or not out[k].is_contiguous() or out[k].numel() < need:
                     raise ValueError(f"export_subtrees: out[{k!r}] must be a contiguous {dt} tensor on {dev} with at "
@@ -454,8 +460,10 @@ class Arena:
         call("spmcts_tree_export_work_bytes", self.h, n, M, ctypes.byref(nbytes))
         work = torch.empty((nbytes.value + 7) // 8, dtype=torch.int64, device=dev)
         depth = -1 if max_depth is None else int(max_depth)
-        call("spmcts_tree_export_batch", self.h, ptr(t), n, M, int(min_visits), depth,
-             *[ptr(out[k]) for k, _, _ in self.EXPORT_FIELDS], ptr(out["count"]), ptr(work), nbytes.value, _stream())
+        call("spmcts_tree_export_bounds_batch" if bounds else "spmcts_tree_export_batch", self.h, ptr(t), n, M,
+             int(min_visits), depth, *[ptr(out[k]) for k, _, _ in self.EXPORT_FIELDS], ptr(out["count"]),
+             *[ptr(out[k]) for k, _, _ in (self.EXPORT_BOUND_FIELDS if bounds else ())], ptr(work), nbytes.value,
+             _stream())
         self._export_keep = (t, work)  # alive until the kernel has run
         return out
 
@@ -476,6 +484,42 @@ class Arena:
                    nodes=torch.zeros(n, dtype=torch.int32, device=dev))
         call("spmcts_tree_bounds_batch", self.h, ptr(t), n, *[ptr(out[k]) for k in self.BOUNDS_FIELDS], _stream())
         self._bounds_trees = t  # alive until the kernel has run
+        return out
+
+    # ------------------------------------------------------------------ stored score bounds
+    stored_bounds = False
+
+    def set_stored_bounds(self):
+        """Keep the score bounds in the nodes from now on (include/spmcts.h spmcts_set_solver_search): every child
+        block carries its moves' move_lo / move_hi, stamped when the block is created and carried up the expansion's
+        path, so that they equal bounds_batch's walk on the tree as it stands.  The search does not read them (its
+        results are bit-identical); the proof-play verdict, proof_moves_batch and proof_stop then read the root's
+        block and walk nothing, and export_subtrees(bounds=True) lists them.  Before the first search only;
+        synchronises; cannot be switched off."""
+        self.set_solver_search(False)
+
+    def set_solver_search(self, on=False):
+        """include/spmcts.h spmcts_set_solver_search: `on`, True / False for every tree or one flag per tree, says
+        whose search uses the stored bounds; the first call starts their maintenance for the whole arena (before
+        the first search only).  This version builds the maintenance alone: a flag that is on raises SpmctsError
+        (-2) and changes nothing, and set_solver_search(False) is set_stored_bounds().  Synchronises."""
+        torch.cuda.current_stream().synchronize()
+        if isinstance(on, (bool, int, np.bool_)):
+            flags = np.full(self.n_trees, 1 if on else 0, dtype=np.uint8)
+        else:
+            flags = np.ascontiguousarray(np.asarray(on, dtype=bool).astype(np.uint8))
+            if flags.shape != (self.n_trees,):
+                raise ValueError(f"expected {self.n_trees} per-tree entries, got {flags.shape}")
+        call("spmcts_set_solver_search", self.h, flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+        self.stored_bounds = True
+
+    def search_progress(self):
+        """Per tree, device int32 [T] each, no host sync (spmcts_search_progress): started, the search_node calls
+        the current search has started (0x3fffffff: none in progress, or stopped by proof_stop); resume, the slot
+        the tree's cycle goes on at * 2, + 1 while the sim cap has it paused inside a fill."""
+        out = dict(started=torch.empty(self.n_trees, dtype=torch.int32, device=self.device),
+                   resume=torch.empty(self.n_trees, dtype=torch.int32, device=self.device))
+        call("spmcts_search_progress", self.h, ptr(out["started"]), ptr(out["resume"]), _stream())
         return out
 
     # ------------------------------------------------------------------ proof-guided play

@@ -3,7 +3,8 @@
 // ----------------------------------------------------------------------------
 // kernel: expand + backup of network-evaluated leaves (mcts.py:316-321, :94-98)
 // ----------------------------------------------------------------------------
-template <class G>
+// SB (arena_solver.h): the new block is stamped with its moves' score bounds and the change carried up the path.
+template <class G, bool SB = false>
 __global__ __launch_bounds__(64) void k_expand(View v, const float *probs0, const float *values0,
                                                const float *probs1, const float *values1) {
   constexpr int P = G::APAD;
@@ -52,6 +53,11 @@ __global__ __launch_bounds__(64) void k_expand(View v, const float *probs0, cons
     v.cnt[(size_t)tree * C_NCNT + C_NN] += 1;
     v.cnt[(size_t)tree * C_NCNT + C_HWM] = max(v.cnt[(size_t)tree * C_NCNT + C_HWM], (int64_t)(blk + 1));
   }
+  if constexpr (SB) {  // (the one expansion of this tree in the launch: nothing it reads was written here)
+    int lo, hi;
+    sb_stamp<G>(v, nb, blk, Board{v.lpos[tree], v.lneg[tree]}, -mover, lane, lo, hi);
+    sb_propagate<G>(v, nb, leaf, plen, lo, hi, lane, [&](int k) { return v.pnode[pb + k]; });
+  }
 }
 
 // ----------------------------------------------------------------------------
@@ -82,7 +88,7 @@ constexpr int EXPAND_THREADS = 256;
 // short dependent LDS / permute / FP64 latencies, not memory round trips): DESIGN.md §4.
 constexpr int SELECT_THREADS = 64;
 
-template <class G, int THREADS, bool ROWS>
+template <class G, int THREADS, bool ROWS, bool SB = false>
 __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, const float *values0,
                                                const float *probs1, const float *values1) {
   constexpr int P = G::APAD;
@@ -269,6 +275,20 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
         }
         if (group_or<P>(unc)) sf.dirty = true;
       }
+      if constexpr (SB) {
+        // stored bounds (arena_solver.h): stamp the new block, carry the change up the slot's path.  The entries
+        // the walk reads may have been written by an earlier slot's walk of this launch: StoreFence's rule
+        int lo, hi;
+        sb_stamp<G>(v, nb, blk, Board{lpos, lneg}, -mover, lane, lo, hi);
+        sf.dirty = true;
+        if (plen > 0) {
+          sf.fence_if_dirty();
+          if (sb_propagate<G>(v, nb, leaf, plen, lo, hi, lane, [&](int k) {
+                return k < P ? s_pnode[grp][j][k] : v.pnode[(size_t)ps * G::MAXD + k];
+              }))
+            sf.dirty = true;
+        }
+      }
       if (lane == 0) {
         v.used[tree] = blk + 1;
         v.need[ps] = NEED_EMPTY;
@@ -331,16 +351,16 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
   }
 }
 
-template <class G>
+template <class G, bool SB = false>
 __global__ __launch_bounds__(EXPAND_THREADS) void k_expand_vl(View v, const float *probs0, const float *values0,
                                                   const float *probs1, const float *values1) {
-  expand_vl_body<G, EXPAND_THREADS, true>(v, probs0, values0, probs1, values1);
+  expand_vl_body<G, EXPAND_THREADS, true, SB>(v, probs0, values0, probs1, values1);
 }
 
 // (its domain: the active list, View::dn = its length, dpack = 1: spmcts_select_tree)
-template <class G>
+template <class G, bool SB = false>
 __global__ __launch_bounds__(SELECT_THREADS) void k_select_vl(View v) {
-  expand_vl_body<G, SELECT_THREADS, false>(v, nullptr, nullptr, nullptr, nullptr);
+  expand_vl_body<G, SELECT_THREADS, false, SB>(v, nullptr, nullptr, nullptr, nullptr);
 }
 
 // ----------------------------------------------------------------------------

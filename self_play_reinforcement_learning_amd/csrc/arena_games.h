@@ -3,7 +3,7 @@
 // ----------------------------------------------------------------------------
 // games: SelfPlayer.play_episode state machine (selfplayworker.py:164-224)
 // ----------------------------------------------------------------------------
-template <class G>
+template <class G, bool SB = false>
 __device__ void start_game(const View &v, int g, int64_t id, const float *priors) {
   const bool swap = (id & 1) != 0;  // swap_sides = not i % 2 == 0 (self_play_parallel.py:237)
   v.gpos[g] = 0;
@@ -16,8 +16,8 @@ __device__ void start_game(const View &v, int g, int64_t id, const float *priors
   v.mv_count[2 * g] = 0;
   v.mv_count[2 * g + 1] = 0;
   // policy.reset(-1 if swap else 1), opposing.reset(1 if swap else -1)  (:175-176)
-  reset_tree<G>(v, 2 * g, swap ? -1 : 1, priors ? priors : v.root_prior + 16 * v.tnet[2 * g]);
-  reset_tree<G>(v, 2 * g + 1, swap ? 1 : -1, priors ? priors + G::A : v.root_prior + 16 * v.tnet[2 * g + 1]);
+  reset_tree<G, SB>(v, 2 * g, swap ? -1 : 1, priors ? priors : v.root_prior + 16 * v.tnet[2 * g]);
+  reset_tree<G, SB>(v, 2 * g + 1, swap ? 1 : -1, priors ? priors + G::A : v.root_prior + 16 * v.tnet[2 * g + 1]);
   if (v.book_n) {  // ids 2k and 2k + 1 play the same opening, once per colour
     const int64_t i = v.book_period ? id % v.book_period : id;
     const int o = (int)((i >> 1) % v.book_n);
@@ -26,7 +26,7 @@ __device__ void start_game(const View &v, int g, int64_t id, const float *priors
   }
 }
 
-template <class G>
+template <class G, bool SB = false>
 __global__ void k_games_start(View v, const int32_t *slots, const float *priors, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -35,7 +35,7 @@ __global__ void k_games_start(View v, const int32_t *slots, const float *priors,
     set_err(v, SPMCTS_ERR_STATE);
     return;
   }
-  start_game<G>(v, g, v.gcnt[7] + i, priors ? priors + (size_t)i * 2 * G::A : nullptr);
+  start_game<G, SB>(v, g, v.gcnt[7] + i, priors ? priors + (size_t)i * 2 * G::A : nullptr);
 }
 
 __global__ void k_games_bump_id(View v, int n) { v.gcnt[7] += n; }
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(1024) void k_games_finish_scan(View v, int refill, 
   }
 }
 
-template <class G>
+template <class G, bool SB = false>
 __global__ void k_games_finish_apply(View v) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= v.G) return;
@@ -293,7 +293,7 @@ __global__ void k_games_finish_apply(View v) {
   }
   const int64_t started = ((const int64_t *)(v.gscratch + 2 * v.G + 2))[0];
   if (fin_idx < can) {
-    start_game<G>(v, g, started + fin_idx, nullptr);
+    start_game<G, SB>(v, g, started + fin_idx, nullptr);
   } else {
     v.gstate[g] = GS_IDLE;
   }

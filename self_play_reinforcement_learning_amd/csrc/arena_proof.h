@@ -25,7 +25,8 @@ enum { PF_MODE_LIST = 0, PF_MODE_GAMES = 1, PF_MODE_ACTIVE = 2 };
 // k_search_end; n = the active list's length): tree active[i]; both write row `tree` of View::pf_*, count the ply
 // in pf_stats, and give a tree whose flag is off, that belongs to no MCTS player or whose game is in its opening
 // book PF_ALL and TB_NONE without a walk.  Any output may be null.
-template <class G>
+// SB: the root's bounds come from its stored block (bounds_root), not from a walk.
+template <class G, bool SB = false>
 __global__ __launch_bounds__(TB_THREADS) void k_proof_verdict(View v, const int32_t *trees, int n, int mode,
                                                               uint32_t *keep_out, int8_t *lo_out, int8_t *hi_out) {
   constexpr int P = G::APAD;
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(TB_THREADS) void k_proof_verdict(View v, const int3
   int rmlo = TB_NONE, rmhi = TB_NONE, lo = TB_NONE, hi = TB_NONE, e0 = 0, nodes = 0;
   uint32_t keep = PF_ALL;
   if (walk) {
-    if (!bounds_walk<G>(v, tree, lane, grp, s_stk, rmlo, rmhi, lo, hi, e0, nodes)) {
+    if (!bounds_root<G, SB>(v, tree, lane, grp, s_stk, rmlo, rmhi, lo, hi, e0, nodes)) {
       if (lane == 0) set_err(v, SPMCTS_ERR_STATE);
       return;
     }
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(TB_THREADS) void k_proof_verdict(View v, const int3
 // lo == hi, tstarted takes the "no sims left" value: the state of a search whose sims have all been started, so
 // the expand replies its pending slots on its !refill path, the select passes it over, and play_move_choice's
 // completeness check holds.  draw_noise resets tstarted at the next search; budget[] stays (k_compact sizes by it).
-template <class G>
+template <class G, bool SB = false>
 __global__ __launch_bounds__(TB_THREADS) void k_proof_stop(View v) {
   constexpr int P = G::APAD;
   __shared__ typename TbGrid<G>::Stack s_stk;
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(TB_THREADS) void k_proof_stop(View v) {
   const int limit = min(v.budget[tree], v.iters), started = v.tstarted[tree];
   if (started >= limit || (v.tres[tree] & RES_FILL)) return;
   int rmlo, rmhi, lo, hi, e0, nodes;
-  if (!bounds_walk<G>(v, tree, lane, grp, s_stk, rmlo, rmhi, lo, hi, e0, nodes)) {
+  if (!bounds_root<G, SB>(v, tree, lane, grp, s_stk, rmlo, rmhi, lo, hi, e0, nodes)) {
     if (lane == 0) set_err(v, SPMCTS_ERR_STATE);
     return;
   }

@@ -3,7 +3,12 @@
 // ----------------------------------------------------------------------------
 // small helpers
 // ----------------------------------------------------------------------------
+// (arena_solver.h, included later: the stored bounds' classification of a move from the board alone)
 template <class G>
+__device__ __forceinline__ int sb_classify(Board b, int player, int lane, int &mlo, int &mhi);
+
+// SB (arena_solver.h): the root block is stamped with the empty board's stored bounds.
+template <class G, bool SB = false>
 __device__ __forceinline__ void reset_tree(const View &v, int tree, int player, const float *prior) {
   constexpr int P = G::APAD;
   const size_t nb = nbase<G>(v, tree);
@@ -24,6 +29,14 @@ __device__ __forceinline__ void reset_tree(const View &v, int tree, int player, 
     nd_p<P>(v, nb + P + j) = j < G::A ? prior[j] : 0.f;
     nd_c<P>(v, nb + P + j) = -1;
     nd_f<P>(v, nb + P + j) = 0;
+  }
+  if constexpr (SB) {
+    for (int j = 0; j < P; ++j) {  // (one thread resets the tree: every entry in turn, pad entries included)
+      int mlo, mhi;
+      sb_classify<G>(Board{0, 0}, player, j, mlo, mhi);
+      nd_lo<P>(v, nb + P + j) = (int8_t)mlo;
+      nd_hi<P>(v, nb + P + j) = (int8_t)mhi;
+    }
   }
   nd_vm<P>(v, bb + 0) = 1u;
   nd_vm<P>(v, bb + 1) = legal_mask<G>(Board{0, 0});
@@ -97,7 +110,7 @@ __device__ void draw_noise(const View &v, int tree) {
 // ----------------------------------------------------------------------------
 // kernels: resets / noise
 // ----------------------------------------------------------------------------
-template <class G>
+template <class G, bool SB = false>
 __global__ void k_tree_reset(View v, const int32_t *trees, const int8_t *players, const float *priors, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -106,7 +119,7 @@ __global__ void k_tree_reset(View v, const int32_t *trees, const int8_t *players
     set_err(v, SPMCTS_ERR_STATE);
     return;
   }
-  reset_tree<G>(v, t, players[i], priors ? priors + (size_t)i * G::A : v.root_prior + 16 * v.tnet[t]);
+  reset_tree<G, SB>(v, t, players[i], priors ? priors + (size_t)i * G::A : v.root_prior + 16 * v.tnet[t]);
 }
 
 template <class G>
@@ -136,7 +149,8 @@ __global__ void k_search_begin(View v, const int32_t *trees, int n) {
 //     so it lands at block 1 and the relation "child block > parent block" is preserved.
 // Results are unchanged bit for bit (tests run the parity fixtures with a tiny blocks_per_tree).
 // Without an explicit blocks_per_tree the store is sized for the worst case and this never runs.
-template <class G>
+// SB (arena_solver.h): the blocks' stored bounds move with the rest of the record.
+template <class G, bool SB = false>
 __global__ __launch_bounds__(256) void k_compact(View v, int n_active) {
   constexpr int P = G::APAD;
   constexpr int NT = 256;
@@ -232,6 +246,7 @@ __global__ __launch_bounds__(256) void k_compact(View v, int n_active) {
     float pr = 0.f;
     uint8_t f = 0;
     uint32_t vm = 0;
+    int8_t blo = 0, bhi = 0;
     if (dst >= 0) {
       const size_t i = nb + (size_t)b * P + j;
       n = nd_n<P>(v, i);
@@ -240,6 +255,10 @@ __global__ __launch_bounds__(256) void k_compact(View v, int n_active) {
       c = nd_c<P>(v, i);
       f = nd_f<P>(v, i);
       if (v.K > 1) vl = nd_vl<P>(v, i);
+      if constexpr (SB) {
+        blo = nd_lo<P>(v, i);
+        bhi = nd_hi<P>(v, i);
+      }
       if (j == 0) vm = nd_vm<P>(v, bb + b);
       if (c >= 0) c = map[c];
     }
@@ -252,6 +271,10 @@ __global__ __launch_bounds__(256) void k_compact(View v, int n_active) {
       nd_c<P>(v, o) = c;
       nd_f<P>(v, o) = f;
       if (v.K > 1) nd_vl<P>(v, o) = vl;
+      if constexpr (SB) {
+        nd_lo<P>(v, o) = blo;
+        nd_hi<P>(v, o) = bhi;
+      }
       if (j == 0) nd_vm<P>(v, bb + dst) = vm;
     }
     __threadfence_block();

@@ -38,6 +38,9 @@ struct TreeExportOut {
   int8_t *player;
   uint8_t *flags;
   int32_t *count;  // [n]
+  // spmcts_tree_export_bounds_batch only (null otherwise): the node's stored entry, the bounds of the move into it
+  // seen from its parent (arena_solver.h); -128 in the root's row
+  int8_t *move_lo, *move_hi;
 };
 
 enum { PV_END_CUT = 0, PV_END_NO_CHILD = 1, PV_END_GAME = 2 };
@@ -173,6 +176,8 @@ __global__ void k_tree_export(View v, const int32_t *trees, int n, int max_nodes
     if (o.p) o.p[row] = nd_p<P>(v, root);
     if (o.player) o.player[row] = (int8_t)rplayer;
     if (o.flags) o.flags[row] = (uint8_t)((tree_block_ok(v, rcb) ? TREE_EXPANDED : 0) | TREE_VALID);
+    if (o.move_lo) o.move_lo[row] = -128;
+    if (o.move_hi) o.move_hi[row] = -128;
     wave_store(wpos, v.rpos[tree]);
     wave_store(wneg, v.rneg[tree]);
     wave_store(wcd, tree_pack(rcb, 0));
@@ -213,6 +218,8 @@ __global__ void k_tree_export(View v, const int32_t *trees, int n, int max_nodes
       if (o.flags)
         o.flags[at] = (uint8_t)((tree_block_ok(v, cc) ? TREE_EXPANDED : 0) | (valid ? TREE_VALID : 0) |
                                 (term ? TREE_TERMINAL : 0));
+      if (o.move_lo) o.move_lo[at] = nd_lo<P>(v, ci);
+      if (o.move_hi) o.move_hi[at] = nd_hi<P>(v, ci);
       wave_store(wpos + idx, nbd.pos);
       wave_store(wneg + idx, nbd.neg);
       wave_store(wcd + idx, tree_pack(cc, depth + 1));
@@ -270,12 +277,7 @@ enum { TB_THREADS = 64, TB_NONE = -128 };
 // the largest x of the group, in every lane
 template <int P>
 __device__ __forceinline__ int group_max(int x) {
-  static_assert(P == 8 || P == 16, "tree groups of 8 or 16 lanes");
-  x = max(x, dpp_i<DPP_XOR1>(x));
-  x = max(x, dpp_i<DPP_XOR2>(x));
-  x = max(x, dpp_i<DPP_HALF_MIRROR>(x));
-  if constexpr (P == 16) x = max(x, dpp_i<DPP_MIRROR>(x));
-  return x;
+  return sb_group_max<P>(x);  // (arena_solver.h: the stamp of a new block takes the same maxima)
 }
 
 // A frame's third word: child block | children still to descend into << 32 | (lo + 128) << 48 | (hi + 128) << 56.
@@ -294,25 +296,13 @@ template <class G>
 __device__ __forceinline__ void bounds_enter(const View &v, size_t nb, Board b, int player, int cb, int lane,
                                              bool room, int &mlo, int &mhi, int &lo, int &hi, uint32_t &dm) {
   constexpr int P = G::APAD;
-  const uint64_t occ = b.pos | b.neg;
-  const int e = G::CELLS - popc(occ);
-  mlo = mhi = TB_NONE;
+  static_assert((int)SB_NONE == (int)TB_NONE, "one code for an illegal move");
   bool desc = false;
-  if (lane < G::A) {
-    Board nbd = b;
-    int rew = 0, done = 0;
-    if (step<G>(nbd, lane, player, &rew, &done) == STEP_OK && (nbd.pos | nbd.neg) != occ) {
-      if (done) {
-        mlo = mhi = rew ? e : 0;
-      } else {
-        const int cc = tree_block_ok(v, cb) ? nd_c<P>(v, nb + (size_t)cb * P + lane) : -1;
-        if (tree_block_ok(v, cc) && room) {
-          desc = true;
-        } else {
-          mlo = -(e - 1);
-          mhi = e - 2;
-        }
-      }
+  if (sb_classify<G>(b, player, lane, mlo, mhi) == SB_OPEN) {  // (arena_solver.h: the stored bounds' stamp)
+    const int cc = tree_block_ok(v, cb) ? nd_c<P>(v, nb + (size_t)cb * P + lane) : -1;
+    if (tree_block_ok(v, cc) && room) {
+      desc = true;
+      mlo = mhi = TB_NONE;
     }
   }
   lo = group_max<P>(mlo);
@@ -384,6 +374,32 @@ __device__ __forceinline__ bool bounds_walk(const View &v, int tree, int lane, i
     }
   }
   return false;
+}
+
+// The root's bounds for arena_proof.h's kernels.  SB (the arena keeps stored bounds, arena_solver.h) and the root
+// has a child block: one read of that block, whose entries are the walk's rmlo / rmhi by the stored bounds'
+// invariant; nodes is 0.  Otherwise the walk (for a root without a block that is its board-only path).
+template <class G, bool SB>
+__device__ __forceinline__ bool bounds_root(const View &v, int tree, int lane, int grp,
+                                            typename TbGrid<G>::Stack &s_stk, int &rmlo, int &rmhi, int &lo, int &hi,
+                                            int &e0, int &nodes) {
+  constexpr int P = G::APAD;
+  if constexpr (SB) {
+    static_assert((int)SB_NONE == (int)TB_NONE, "one code for an illegal move");
+    const size_t nb = nbase<G>(v, tree);
+    const int cb = nd_c<P>(v, nb + v.root[tree]);
+    if (tree_block_ok(v, cb)) {
+      const size_t ci = nb + (size_t)cb * P + lane;
+      rmlo = nd_lo<P>(v, ci);
+      rmhi = nd_hi<P>(v, ci);
+      lo = group_max<P>(rmlo);
+      hi = group_max<P>(rmhi);
+      e0 = G::CELLS - popc(v.rpos[tree] | v.rneg[tree]);
+      nodes = 0;
+      return true;
+    }
+  }
+  return bounds_walk<G>(v, tree, lane, grp, s_stk, rmlo, rmhi, lo, hi, e0, nodes);
 }
 
 // spmcts_tree_bounds_batch: the walk above for each listed tree, one APAD-lane group per tree.

@@ -166,10 +166,14 @@ enum { BOOK_MAX_OPENINGS = 65536 };
 // 16 P bytes; w, the mask: the next) lie in two 128-byte lines for Connect4 (P = 8) instead of one line
 // per field array.  Node id i = (tree * cap + block) * P + slot, as before; the flag is "w is a numpy
 // float64" (strong_play dtype quirk, mcts.py:287/:308), vl is MCNode.virtual_loss (mcts.py:44).
+// Stored score bounds (arena_solver.h; written only once spmcts_set_solver_search switched them on): lo i8[P] |
+// hi i8[P] in what was pad, the bounds of the move into child j seen from the block's own node.
 template <int P>
 struct NodeRec {
   static constexpr int N = 0, VL = 4 * P, C = 8 * P, PR = 12 * P, W = 16 * P, F = 24 * P, VM = 25 * P, BYTES = 32 * P;
+  static constexpr int LO = 26 * P, HI = 27 * P;
   static_assert(VM + 4 <= BYTES && W % 8 == 0 && VM % 4 == 0, "record layout");
+  static_assert(VM + 4 <= LO && HI + P <= BYTES, "record layout: stored bounds");
 };
 template <int P>
 __host__ __device__ __forceinline__ char *nd_rec(const View &v, size_t i) {
@@ -198,6 +202,14 @@ __host__ __device__ __forceinline__ double &nd_w(const View &v, size_t i) {
 template <int P>
 __host__ __device__ __forceinline__ uint8_t &nd_f(const View &v, size_t i) {
   return ((uint8_t *)(nd_rec<P>(v, i) + NodeRec<P>::F))[i % P];
+}
+template <int P>
+__host__ __device__ __forceinline__ int8_t &nd_lo(const View &v, size_t i) {
+  return ((int8_t *)(nd_rec<P>(v, i) + NodeRec<P>::LO))[i % P];
+}
+template <int P>
+__host__ __device__ __forceinline__ int8_t &nd_hi(const View &v, size_t i) {
+  return ((int8_t *)(nd_rec<P>(v, i) + NodeRec<P>::HI))[i % P];
 }
 // valid-children mask of block `gb` = tree * cap + block
 template <int P>

@@ -30,6 +30,7 @@
 //   arena_rng.h     Philox / tape RNG
 //   arena_select.h  resets and noise, k_compact, DPP reductions, k_select, the threaded sim and slot fill
 //   arena_rows.h    leaf dedup, evaluation cache, peer push, k_scan_need, k_encode
+//   arena_solver.h  score bounds kept in the nodes: the stamp of a new child block, the walk up the expansion's path
 //   arena_expand.h  k_expand, threaded expand and select (one slot-cycle walk), _play, k_search_end, set_node, k_play_action
 //   negamax.h       exact depth-limited negamax: the search core (host and device), its batch and arena kernels
 //   solve.h         exact solver to the end of the game: alpha-beta with a transposition table, resumable launches
@@ -92,6 +93,7 @@ static int fail(int code, const std::string &msg) {
 #include "arena_rng.h"
 #include "arena_select.h"
 #include "arena_rows.h"
+#include "arena_solver.h"
 #include "arena_expand.h"
 #include "negamax.h"
 #include "solve.h"
@@ -150,6 +152,9 @@ struct spmcts_arena {
   // proof-guided play (spmcts_set_proof_play): the View::pf_* arrays' allocations (flags, keep, lo, hi, stats, stop
   // counts), kept while the feature is off for every tree (View::pf_keep null)
   std::vector<void *> proof_allocs;
+  // stored score bounds (spmcts_set_solver_search, arena_solver.h): the arena launches the SB = true kernels
+  // (LAUNCH_SB below), the resets' among them
+  bool sb = false;
 };
 
 static bool league_on(const spmcts_arena *h) { return h->lg.n > 0; }
@@ -376,6 +381,12 @@ static int launch(void (*k)(P...), long long n, int B, hipStream_t s, const A &.
 // launch() of a kernel template on the arena's game type: k<G>, G from with_game
 #define LAUNCH(h, k, n, B, s, ...) \
   with_game((h)->cfg.game, (h)->W, (h)->H, [&](auto game_) { return launch(k<decltype(game_)>, n, B, s, __VA_ARGS__); })
+// the same for a kernel template <class G, bool SB>: the stored-bounds instantiation once the arena keeps them
+#define LAUNCH_SB(h, k, n, B, s, ...)                                                                       \
+  with_game((h)->cfg.game, (h)->W, (h)->H, [&](auto game_) {                                                \
+    return (h)->sb ? launch(k<decltype(game_), true>, n, B, s, __VA_ARGS__)                                 \
+                   : launch(k<decltype(game_), false>, n, B, s, __VA_ARGS__);                               \
+  })
 
 // ---- negamax launches --------------------------------------------------------
 // A launch's worst-case node bound, positions * sum_{k = 1 .. D} A^k, stays below NM_LAUNCH_NODES: a batch (and
@@ -477,6 +488,7 @@ int spmcts_arena_create(const spmcts_config *cfg, int device, spmcts_arena **out
     *it.first = p;
   }
   if (h->v.K > 1) (void)hipMemset(h->v.dtab, 0, sizeof(uint64_t) * ((size_t)h->v.dmask + 1));  // generation 0
+  (void)hipMemset(h->v.used, 0, sizeof(int32_t) * (size_t)h->v.T);  // no blocks before a reset (spmcts_set_solver_search reads it)
   enqueue(k_rng_init, h->v.T, 256, nullptr, h->v, cfg->seed, cfg->subsequence0);  // (a failed launch surfaces at the synchronize below)
   enqueue(k_games_init, h->v.G, 256, nullptr, h->v);
   // default root prior: uniform (replaced by spmcts_set_root_prior)
@@ -594,7 +606,7 @@ int spmcts_tree_reset(spmcts_arena *h, const int32_t *trees_dev, const int8_t *r
                       const float *priors_dev, int32_t n, spmcts_stream stream) {
   if (!h) return fail(-1, "null arena");
   if (n <= 0) return 0;
-  return LAUNCH(h, k_tree_reset, n, 128, (hipStream_t)stream, h->v, trees_dev, root_player_dev, priors_dev, n);
+  return LAUNCH_SB(h, k_tree_reset, n, 128, (hipStream_t)stream, h->v, trees_dev, root_player_dev, priors_dev, n);
 }
 
 int spmcts_search_begin(spmcts_arena *h, const int32_t *trees_dev, int32_t n, spmcts_stream stream) {
@@ -606,7 +618,7 @@ int spmcts_search_begin(spmcts_arena *h, const int32_t *trees_dev, int32_t n, sp
   if (h->v.cwin) ++h->v.cgen;  // a new evaluation-cache generation per search
   if (n <= 0) return 0;
   TRY(LAUNCH(h, k_search_begin, n, 128, (hipStream_t)stream, h->v, trees_dev, n));
-  if (h->v.gc) TRY(LAUNCH(h, k_compact, 256ll * n, 256, (hipStream_t)stream, h->v, n));  // one block per tree
+  if (h->v.gc) TRY(LAUNCH_SB(h, k_compact, 256ll * n, 256, (hipStream_t)stream, h->v, n));  // one block per tree
   return 0;
 }
 
@@ -697,7 +709,7 @@ int spmcts_select_tree(spmcts_arena *h, spmcts_stream stream) {
     const long long lanes = (long long)n * h->P;
     View dv = h->v;  // k_select_vl walks the active list as a packed domain
     set_domain(h, dv, true);
-    rc = h->v.K > 1 ? LAUNCH(h, k_select_vl, lanes, SELECT_THREADS, s, dv) : LAUNCH(h, k_select, lanes, 64, s, h->v, n);
+    rc = h->v.K > 1 ? LAUNCH_SB(h, k_select_vl, lanes, SELECT_THREADS, s, dv) : LAUNCH(h, k_select, lanes, 64, s, h->v, n);
   }
   h->v.sim += h->v.K;
   return rc;
@@ -731,10 +743,10 @@ int spmcts_expand2(spmcts_arena *h, const float *probs0_dev, const float *values
     h->cache_step = false;
   }
   if (h->v.K > 1)  // one P-lane group per tree of the domain
-    return LAUNCH(h, k_expand_vl, (long long)dv.dn * h->P, EXPAND_THREADS, (hipStream_t)stream, dv, probs0_dev,
-                  values0_dev, probs1_dev, values1_dev);
+    return LAUNCH_SB(h, k_expand_vl, (long long)dv.dn * h->P, EXPAND_THREADS, (hipStream_t)stream, dv, probs0_dev,
+                     values0_dev, probs1_dev, values1_dev);
   const long long lanes = (long long)h->v.T * h->P;  // one P-lane group per row
-  return LAUNCH(h, k_expand, lanes, 64, (hipStream_t)stream, h->v, probs0_dev, values0_dev, probs1_dev, values1_dev);
+  return LAUNCH_SB(h, k_expand, lanes, 64, (hipStream_t)stream, h->v, probs0_dev, values0_dev, probs1_dev, values1_dev);
 }
 
 int spmcts_expand(spmcts_arena *h, const float *probs_dev, const float *values_dev, spmcts_stream stream) {
@@ -834,6 +846,14 @@ int spmcts_set_sim_cap(spmcts_arena *h, int32_t cap) {
   // below 2 K a search could need more launches than ceil(iterations / K) + 1 (arena_select.h "sim cap")
   if (cap < 0 || (cap > 0 && cap < 2 * h->v.K)) return fail(-3, "sim cap: 0 (off) or at least 2 * search_threads");
   h->v.simcap = h->v.K > 1 ? cap : 0;
+  return 0;
+}
+
+int spmcts_search_progress(spmcts_arena *h, int32_t *started_dev, int32_t *resume_dev, spmcts_stream stream) {
+  if (!h) return fail(-1, "null arena");
+  const size_t T = h->v.T;
+  if (started_dev) HIP_TRY(hipMemcpyAsync(started_dev, h->v.tstarted, 4 * T, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (resume_dev) HIP_TRY(hipMemcpyAsync(resume_dev, h->v.tres, 4 * T, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
 }
 
@@ -964,7 +984,7 @@ int spmcts_search_end(spmcts_arena *h, double temp, int32_t *actions_dev, int8_t
   const int n = h->n_active;
   if (n <= 0) return 0;
   if (h->v.pf_keep)  // the active trees' verdicts, read by k_search_end
-    TRY(LAUNCH(h, k_proof_verdict, (long long)n * h->P, TB_THREADS, (hipStream_t)stream, h->v, (const int32_t *)nullptr,
+    TRY(LAUNCH_SB(h, k_proof_verdict, (long long)n * h->P, TB_THREADS, (hipStream_t)stream, h->v, (const int32_t *)nullptr,
                n, (int)PF_MODE_ACTIVE, h->v.pf_keep, h->v.pf_lo, h->v.pf_hi));
   return LAUNCH(h, k_search_end, n, 64, (hipStream_t)stream, h->v, n, temp, actions_dev, states_dev, tree_probs_dev,
                 q_dev, q_f64_dev, recorded_dev);
@@ -1030,7 +1050,7 @@ int spmcts_games_start(spmcts_arena *h, const int32_t *slots_dev, const float *p
   if (h->v.G <= 0) return fail(-4, "arena has no game slots");
   if (n <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  TRY(LAUNCH(h, k_games_start, n, 128, s, h->v, slots_dev, priors_dev, n));
+  TRY(LAUNCH_SB(h, k_games_start, n, 128, s, h->v, slots_dev, priors_dev, n));
   return launch(k_games_bump_id, 1, 1, s, h->v, n);
 }
 
@@ -1048,7 +1068,7 @@ int spmcts_games_begin_ply(spmcts_arena *h, spmcts_stream stream) {
   h->v.sim = 0;
   if (h->v.cwin) ++h->v.cgen;  // a new evaluation-cache generation per ply
   TRY(LAUNCH(h, k_games_begin_ply, h->v.G, 128, (hipStream_t)stream, h->v));
-  if (h->v.gc) TRY(LAUNCH(h, k_compact, 256ll * h->v.G, 256, (hipStream_t)stream, h->v, h->v.G));  // one block per tree
+  if (h->v.gc) TRY(LAUNCH_SB(h, k_compact, 256ll * h->v.G, 256, (hipStream_t)stream, h->v, h->v.G));  // one block per tree
   return 0;
 }
 
@@ -1057,7 +1077,7 @@ int spmcts_games_end_ply(spmcts_arena *h, void *leaves_dev, int32_t *leaf_count_
   hipStream_t s = (hipStream_t)stream;
   if (h->nm_on) TRY(negamax_games(h, s));  // the negamax movers' codes, read by k_games_end_ply
   if (h->v.pf_keep)  // the mover trees' verdicts, read by k_games_end_ply
-    TRY(LAUNCH(h, k_proof_verdict, (long long)h->v.G * h->P, TB_THREADS, s, h->v, (const int32_t *)nullptr, h->v.G,
+    TRY(LAUNCH_SB(h, k_proof_verdict, (long long)h->v.G * h->P, TB_THREADS, s, h->v, (const int32_t *)nullptr, h->v.G,
                (int)PF_MODE_GAMES, h->v.pf_keep, h->v.pf_lo, h->v.pf_hi));
   TRY(LAUNCH(h, k_games_end_ply, h->v.G, 64, s, h->v));
   return launch_rows(h, leaves_dev, leaf_count_dev, s, false);
@@ -1067,7 +1087,7 @@ int spmcts_games_finish_ply(spmcts_arena *h, int32_t refill, int32_t *out_dev, s
   if (!h) return fail(-1, "null arena");
   hipStream_t s = (hipStream_t)stream;
   TRY(LAUNCH(h, k_games_finish_scan, 1024, 1024, s, h->v, refill, out_dev));  // one block
-  return LAUNCH(h, k_games_finish_apply, h->v.G, 64, s, h->v);
+  return LAUNCH_SB(h, k_games_finish_apply, h->v.G, 64, s, h->v);
 }
 
 int spmcts_export_moves(spmcts_arena *h, int8_t *states_dev, float *tree_probs_dev, double *q_dev, uint8_t *q_f64_dev,
@@ -1224,11 +1244,34 @@ int spmcts_tree_export_work_bytes(spmcts_arena *h, int32_t n, int32_t max_nodes,
   });
 }
 
+static int tree_export(spmcts_arena *h, const int32_t *trees_dev, int32_t n, int32_t max_nodes, int32_t min_visits,
+                       int32_t max_depth, TreeExportOut o, void *work_dev, uint64_t work_bytes, spmcts_stream stream);
+
 int spmcts_tree_export_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n, int32_t max_nodes,
                              int32_t min_visits, int32_t max_depth, int32_t *parent_dev, int8_t *action_dev,
                              int16_t *depth_dev, int32_t *node_n_dev, int32_t *node_vl_dev, double *node_w_dev,
                              float *node_p_dev, int8_t *player_dev, uint8_t *flags_dev, int32_t *count_dev,
                              void *work_dev, uint64_t work_bytes, spmcts_stream stream) {
+  const TreeExportOut o{parent_dev, action_dev, depth_dev, node_n_dev, node_vl_dev, node_w_dev, node_p_dev, player_dev,
+                        flags_dev, count_dev, nullptr, nullptr};
+  return tree_export(h, trees_dev, n, max_nodes, min_visits, max_depth, o, work_dev, work_bytes, stream);
+}
+
+int spmcts_tree_export_bounds_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t n, int32_t max_nodes,
+                                    int32_t min_visits, int32_t max_depth, int32_t *parent_dev, int8_t *action_dev,
+                                    int16_t *depth_dev, int32_t *node_n_dev, int32_t *node_vl_dev, double *node_w_dev,
+                                    float *node_p_dev, int8_t *player_dev, uint8_t *flags_dev, int32_t *count_dev,
+                                    int8_t *move_lo_dev, int8_t *move_hi_dev, void *work_dev, uint64_t work_bytes,
+                                    spmcts_stream stream) {
+  if (!h) return fail(-1, "null arena");
+  if (!h->sb) return fail(-4, "the arena keeps no stored bounds (spmcts_set_solver_search)");
+  const TreeExportOut o{parent_dev, action_dev, depth_dev, node_n_dev, node_vl_dev, node_w_dev, node_p_dev, player_dev,
+                        flags_dev, count_dev, move_lo_dev, move_hi_dev};
+  return tree_export(h, trees_dev, n, max_nodes, min_visits, max_depth, o, work_dev, work_bytes, stream);
+}
+
+static int tree_export(spmcts_arena *h, const int32_t *trees_dev, int32_t n, int32_t max_nodes, int32_t min_visits,
+                       int32_t max_depth, TreeExportOut o, void *work_dev, uint64_t work_bytes, spmcts_stream stream) {
   if (!h) return fail(-1, "null arena");
   if (n < 0) return fail(-3, "tree_export: n must not be negative");
   if (max_nodes < 1) return fail(-3, "tree_export: max_nodes must be at least 1");
@@ -1239,8 +1282,6 @@ int spmcts_tree_export_batch(spmcts_arena *h, const int32_t *trees_dev, int32_t 
   if (!trees_dev || !work_dev) return fail(-1, "null argument");
   if (work_bytes < need || ((uintptr_t)work_dev & 7))
     return fail(-3, "tree_export: work buffer too small or not 8-byte aligned (spmcts_tree_export_work_bytes)");
-  const TreeExportOut o{parent_dev, action_dev, depth_dev, node_n_dev, node_vl_dev, node_w_dev, node_p_dev, player_dev,
-                        flags_dev, count_dev};
   return LAUNCH(h, k_tree_export, (long long)n * h->P, 256, (hipStream_t)stream, h->v, trees_dev, n, max_nodes,
                 min_visits, max_depth, o, (uint64_t *)work_dev);
 }
@@ -1303,8 +1344,8 @@ int spmcts_tree_proof_moves_batch(spmcts_arena *h, const int32_t *trees_dev, int
   if (n < 0) return fail(-3, "tree_proof_moves: n must not be negative");
   if (n == 0) return 0;
   if (!trees_dev) return fail(-1, "null argument");
-  return LAUNCH(h, k_proof_verdict, (long long)n * h->P, TB_THREADS, (hipStream_t)stream, h->v, trees_dev, n,
-                (int)PF_MODE_LIST, keep_dev, lo_dev, hi_dev);
+  return LAUNCH_SB(h, k_proof_verdict, (long long)n * h->P, TB_THREADS, (hipStream_t)stream, h->v, trees_dev, n,
+                   (int)PF_MODE_LIST, keep_dev, lo_dev, hi_dev);
 }
 
 int spmcts_proof_last(spmcts_arena *h, uint32_t *keep_dev, int8_t *lo_dev, int8_t *hi_dev, spmcts_stream stream) {
@@ -1344,7 +1385,34 @@ int spmcts_proof_stop(spmcts_arena *h, spmcts_stream stream) {
   if (!h) return fail(-1, "null arena");
   if (h->v.K <= 1) return fail(-4, "proof_stop needs search_threads > 1 (a sequential search has no sims left to skip)");
   if (!h->v.pf_keep) return fail(-4, "proof_stop needs proof play (spmcts_set_proof_play)");
-  return LAUNCH(h, k_proof_stop, (long long)h->v.T * h->P, TB_THREADS, (hipStream_t)stream, h->v);
+  return LAUNCH_SB(h, k_proof_stop, (long long)h->v.T * h->P, TB_THREADS, (hipStream_t)stream, h->v);
+}
+
+// ---- stored score bounds -----------------------------------------------------
+int spmcts_set_solver_search(spmcts_arena *h, const uint8_t *on) {
+  if (!h) return fail(-1, "null arena");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  // the use flags: the search rules that read the stored bounds are not built, so no tree can use them yet
+  bool any = !on;
+  if (on)
+    for (int t = 0; t < h->v.T; ++t) any |= on[t] != 0;
+  if (any) return fail(-2, "solver search: the search rules are not built in this version (every use flag must be 0)");
+  if (h->sb) return 0;
+  // every block that exists must carry its bounds: only the root blocks may exist, and those are stamped here
+  std::vector<int32_t> used(h->v.T);
+  HIP_TRY(hipMemcpy(used.data(), h->v.used, 4 * (size_t)h->v.T, hipMemcpyDeviceToHost));
+  for (int32_t u : used)
+    if (u > 2) return fail(-4, "solver search must be switched on before the first search (a tree holds more than its root block)");
+  h->sb = true;
+  // the root blocks of the trees reset so far (from here on reset_tree stamps them itself)
+  const int rc = LAUNCH(h, k_sb_stamp_roots, (long long)h->v.T * h->P, 64, (hipStream_t) nullptr, h->v);
+  if (rc) {
+    h->sb = false;
+    return rc;
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  return 0;
 }
 
 // ---- league ---------------------------------------------------------------

@@ -103,8 +103,10 @@ class SelfPlayEngine:
                  opponent_iterations=None, record=True, search_threads=1, leaf_dedup=None, opponent_alpha=None,
                  opponent_strong_play=None, opponent_search_threads=None, eval_cache=None, openings=None,
                  opening_period=0, opponent_depth=2, record_games=False, proof_play=False, opponent_proof_play=None,
-                 proof_stop_every=0):
-        """proof_play: the policy's move choice uses what its tree has proved (Arena.set_proof_play; off by
+                 proof_stop_every=0, stored_bounds=False):
+        """stored_bounds: keep the score bounds in the nodes (Arena.set_stored_bounds; off by default): games are
+        bit-identical, and the proof_play verdict and proof_stop read the root's block instead of walking the tree.
+        proof_play: the policy's move choice uses what its tree has proved (Arena.set_proof_play; off by
         default); opponent_proof_play: the same for the opposing MCTS side, None = the policy's (a hard-coded
         opponent is unaffected either way).  proof_stop_every=N > 0: after every N-th simulation step of a ply a
         searching tree whose root is solved starts no more sims (Arena.proof_stop, queued on the engine's stream
@@ -205,6 +207,9 @@ class SelfPlayEngine:
             raise ValueError("proof_stop_every needs search_threads > 1")
         if self.proof_play:
             self.arena.set_proof_play([pp0, pp1] * n_games)
+        self.stored_bounds = bool(stored_bounds)
+        if self.stored_bounds:  # (no game has started: every tree holds its root block at most)
+            self.arena.set_stored_bounds()
         self.openings = None
         if openings:
             self.openings = validate_openings(game, openings)
@@ -583,8 +588,8 @@ class LanedEngine:
     def __init__(self, game, network, n_games=4096, lanes=2, seed=0, subsequence0=None, device=None, pack=True,
                  stagger=False, cross_dedup=None, lane_sizes=None, **kw):
         # openings= / opening_period= (SelfPlayEngine): every lane gets the same book and assigns it by its
-        # lane-local game ids; proof_play= / opponent_proof_play= / proof_stop_every= reach every lane too (a lane's
-        # proof_stop is queued on its own stream, after the expand of the step)
+        # lane-local game ids; proof_play= / opponent_proof_play= / proof_stop_every= / stored_bounds= reach every
+        # lane too (a lane's proof_stop is queued on its own stream, after the expand of the step)
         if lanes < 1 or n_games < lanes:
             raise ValueError(f"need 1 <= lanes <= n_games (lanes={lanes}, n_games={n_games})")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -916,8 +921,11 @@ class LeagueEngine:
 
     def __init__(self, game, players, pairings, games_per_pairing=100, seed=0, search_threads=4,
                  dtype=torch.float16, subsequence0=0, device=None, leaf_layout="nhwc", cpuct=4.0, x_noise=0.25,
-                 blocks_per_tree=0, openings=None, rng="philox", record_games=False, proof_stop_every=0):
-        """A player dict's "proof_play": True switches proof-guided play on for that player's trees (Arena.
+                 blocks_per_tree=0, openings=None, rng="philox", record_games=False, proof_stop_every=0,
+                 stored_bounds=False):
+        """stored_bounds: the arena keeps the score bounds in the nodes (Arena.set_stored_bounds; for the whole
+        arena, since every tree's expansions maintain them): the same games, the proof_play players' verdicts and
+        proof_stop read the root's block.  A player dict's "proof_play": True switches proof-guided play on for that player's trees (Arena.
         set_proof_play; per player, so one net can meet itself with and without it; a hard-coded player ignores it).
         proof_stop_every=N > 0: after every N-th simulation step of a ply a searching tree with proof play whose root
         is solved starts no more sims (Arena.proof_stop); needs a proof_play player and search_threads > 1.
@@ -1002,6 +1010,9 @@ class LeagueEngine:
             raise ValueError("proof_stop_every needs search_threads > 1")
         if self.proof_play:
             a.set_proof_play(proof)
+        self.stored_bounds = bool(stored_bounds)
+        if self.stored_bounds:  # (no game has started)
+            a.set_stored_bounds()
         self.record_games = bool(record_games)
         self._records = None
         if self.record_games:

@@ -72,7 +72,8 @@ class MCTreeSearch(Policy):
     def __init__(self, network=None, env=None, optim=None, memory_queue=None, iterations=100, temperature_cutoff=5,
                  batch_size=64, memory_size=200000, min_memory=20000, update_nn=True, starting_state_dict=None,
                  thread_count=4, strong_play=False, q_average=True, alpha=1, env_gen=None, evaluator=None,
-                 seed=None, device=None, rng="philox", cpuct=4, x_noise=0.25, threading=False, proof_play=False):
+                 seed=None, device=None, rng="philox", cpuct=4, x_noise=0.25, threading=False, proof_play=False,
+                 stored_bounds=False):
         network = network if network is not None else evaluator
         env = env if env is not None else env_gen
         if network is None or env is None:
@@ -114,6 +115,11 @@ class MCTreeSearch(Policy):
         self.proof_play = bool(proof_play)
         if self.proof_play:
             self._arena.set_proof_play(True)
+        # stored_bounds=True: the tree keeps its score bounds in the nodes (Arena.set_stored_bounds); searches are
+        # bit-identical, proof_moves() and the proof_play verdict read the root's block instead of walking the tree
+        self.stored_bounds = bool(stored_bounds)
+        if self.stored_bounds:
+            self._arena.set_stored_bounds()
         self.temp_memory = []
         self.moves_played = 0
         # weights changed (update_from_memory / load_state_dict): the evaluator's folded / packed copy is
@@ -224,9 +230,10 @@ class MCTreeSearch(Policy):
         from .tree import TreeView
 
         room = 2 + self.iterations * (self.actions if min_visits <= 0 else 1)
-        view = TreeView.from_export(self._arena.export_subtrees([0], room, min_visits, max_depth))
+        sb = self.stored_bounds  # the nodes then carry their stored bounds (TreeNode.move_lo / .move_hi)
+        view = TreeView.from_export(self._arena.export_subtrees([0], room, min_visits, max_depth, bounds=sb))
         if view.truncated:
-            view = TreeView.from_export(self._arena.export_subtrees([0], view.count, min_visits, max_depth))
+            view = TreeView.from_export(self._arena.export_subtrees([0], view.count, min_visits, max_depth, bounds=sb))
         self._arena.check()
         return view
 
@@ -324,7 +331,7 @@ class MCTreeSearch(Policy):
 @torch.no_grad()
 def analyse_positions(game, network, positions, iterations, search_threads=1, x_noise=0.25, seed=0, alpha=1.0,
                       strong_play=False, cpuct=4.0, player=1, device=None, dtype=torch.float16, rng="philox",
-                      pv_len=0, tree=None, bounds=False):
+                      pv_len=0, tree=None, bounds=False, stored_bounds=False):
     """The search's answer for a batch of positions, each a move sequence from the empty board.
 
     One tree-mode arena of one tree per position: reset(player), one play_action step per ply (a tree whose
@@ -343,7 +350,8 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
     has proved (Arena.bounds_batch): bound_lo, bound_hi int8 [n] (lo <= s <= hi for the exact solver's score s),
     move_lo, move_hi int8 [n, A], bound_best int8 [n], bound_nodes int32 [n], and keep int32 [n], the moves
     proof-guided play would choose among (Arena.proof_moves_batch; bit a: move a).  None of them changes the other
-    keys."""
+    keys.  stored_bounds=True keeps the score bounds in the nodes (Arena.set_stored_bounds): the same outputs, `keep`
+    read from the root's stored block, and tree=dict(..., bounds=True) lists the stored entries."""
     from .openings import validate_openings
 
     game = game if isinstance(game, str) else game_of_env(game)
@@ -357,6 +365,9 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
                   strong_play=strong_play, leaf_format=ev.leaf_format, leaf_layout=ev.leaf_layout, cpuct=cpuct,
                   x_noise=x_noise, alpha=alpha, device=dev, search_threads=search_threads)
     try:
+        if stored_bounds:
+            arena.set_stored_bounds()
+
         def eval_expand(count):
             if count:
                 probs, values = ev(arena.leaves(count))

@@ -17,6 +17,7 @@ import numpy as np
 
 FLAG_EXPANDED, FLAG_VALID, FLAG_TERMINAL = 1, 2, 4
 FIELDS = ("parent", "action", "depth", "node_n", "node_vl", "node_w", "node_p", "player", "flags")
+BOUND_FIELDS = ("move_lo", "move_hi")  # export_subtrees(bounds=True): each node's stored entry
 BOUND_ILLEGAL = -128  # move_lo / move_hi of an illegal move, and its code
 
 
@@ -95,13 +96,16 @@ def _env_of(game):
 
 
 class TreeNode:
-    """One exported node: MCNode's n, w, p, player, virtual loss (`vl`) and q, plus where it sits in the tree."""
+    """One exported node: MCNode's n, w, p, player, virtual loss (`vl`) and q, plus where it sits in the tree.
+    move_lo / move_hi: the node's stored score bounds (the move into it, seen from its parent) where the export
+    carried them (Arena.export_subtrees(bounds=True)), else None."""
 
     __slots__ = ("index", "parent", "children", "action", "depth", "n", "vl", "w", "p", "player", "expanded", "valid",
-                 "terminal")
+                 "terminal", "move_lo", "move_hi")
 
-    def __init__(self, index, parent, action, depth, n, vl, w, p, player, flags):
+    def __init__(self, index, parent, action, depth, n, vl, w, p, player, flags, move_lo=None, move_hi=None):
         self.index, self.parent, self.children = index, parent, ()
+        self.move_lo, self.move_hi = move_lo, move_hi
         self.action, self.depth, self.n, self.vl, self.w, self.p, self.player = action, depth, n, vl, w, p, player
         self.expanded = bool(flags & FLAG_EXPANDED)
         self.valid = bool(flags & FLAG_VALID)
@@ -131,14 +135,18 @@ class TreeView:
     qualified on the device) and `truncated` (count > the entries the export had room for)."""
 
     def __init__(self, parent, action, depth, node_n, node_vl, node_w, node_p, player, flags, count=None,
-                 max_nodes=None):
+                 max_nodes=None, move_lo=None, move_hi=None):
         parent = np.asarray(parent).reshape(-1)
         room = len(parent) if max_nodes is None else int(max_nodes)
         self.count = int(room if count is None else count)
         self.max_nodes = room
         m = min(self.count, room, len(parent))
         cols = [np.asarray(x).reshape(-1) for x in (action, depth, node_n, node_vl, node_w, node_p, player, flags)]
-        if any(len(c) < m for c in cols):
+        if (move_lo is None) != (move_hi is None):
+            raise ValueError("TreeView: move_lo and move_hi come together")
+        self.has_bounds = move_lo is not None
+        bcols = [np.asarray(x).reshape(-1) for x in (move_lo, move_hi)] if self.has_bounds else []
+        if any(len(c) < m for c in cols + bcols):
             raise ValueError("TreeView: every array needs an entry per node")
         self.nodes = []
         kids = [[] for _ in range(m)]
@@ -148,7 +156,7 @@ class TreeView:
                 raise ValueError(f"TreeView: entry {i} has parent {pi} (the root comes first, parents before children)")
             a, d, n, vl, w, p, pl, fl = (c[i] for c in cols)
             node = TreeNode(i, self.nodes[pi] if i else None, int(a), int(d), int(n), int(vl), float(w), float(p),
-                            int(pl), int(fl))
+                            int(pl), int(fl), *[int(c[i]) for c in bcols])
             self.nodes.append(node)
             if i:
                 kids[pi].append(node)
@@ -160,19 +168,20 @@ class TreeView:
     @classmethod
     def from_arrays(cls, count=None, max_nodes=None, **arrays):
         """From plain arrays (numpy or lists), one entry per node in export order: parent, action, depth, node_n,
-        node_vl, node_w, node_p, player, flags."""
-        return cls(*[arrays[k] for k in FIELDS], count=count, max_nodes=max_nodes)
+        node_vl, node_w, node_p, player, flags; and, optionally, move_lo and move_hi (the stored bounds)."""
+        return cls(*[arrays[k] for k in FIELDS], count=count, max_nodes=max_nodes,
+                   **{k: arrays[k] for k in BOUND_FIELDS if k in arrays})
 
     @classmethod
     def from_export(cls, out, row=0):
         """From row `row` of Arena.export_subtrees' dict (device tensors; one host copy per field)."""
-        host = {k: out[k][row].cpu().numpy() for k in FIELDS}
+        host = {k: out[k][row].cpu().numpy() for k in FIELDS + BOUND_FIELDS if k in out}
         return cls.from_arrays(count=int(out["count"][row]), max_nodes=int(out["parent"].shape[1]), **host)
 
     @classmethod
     def from_dict(cls, d):
         nodes = d["nodes"]
-        arrays = {k: [nd[k] for nd in nodes] for k in FIELDS}
+        arrays = {k: [nd[k] for nd in nodes] for k in FIELDS + BOUND_FIELDS if k in FIELDS or (nodes and k in nodes[0])}
         return cls.from_arrays(count=d["count"], max_nodes=d["max_nodes"], **arrays)
 
     # ------------------------------------------------------------------ reading
@@ -195,7 +204,7 @@ class TreeView:
             node = best
         return out
 
-    def score_bounds(self, game, board, player):
+    def score_bounds(self, game, board, player, per_node=None):
         """The host twin of Arena.bounds_batch (include/spmcts.h spmcts_tree_bounds_batch; no GPU): what this tree
         proves about the exact score s of its root position, lo <= s <= hi.  game: the arena's game name; board
         [W, H]: the root's board of +-1 stones; player: the side to move there.  The view must hold the whole tree:
@@ -203,7 +212,9 @@ class TreeView:
         that ends the game is worth e, the root's empty cells, for a win and 0 for a full board; a move into an
         expanded node [-hi(child), -lo(child)]; any other [-(e - 1), e - 2]; lo / hi are the maxima over the legal
         moves.  Returns dict(lo, hi, move_lo [A], move_hi [A] (-128: illegal), best (the lowest action with
-        move_lo == lo), empty, nodes (the expanded nodes entered)), plain ints and lists."""
+        move_lo == lo), empty, nodes (the expanded nodes entered)), plain ints and lists.  per_node: a list with an
+        entry per node of the view, filled with (move_lo, move_hi) of the move into each node below the root as seen
+        from its parent (node_bounds)."""
         env, W, H, A = _env_of(game)
         if self.truncated or self.root is None:
             raise ValueError("score_bounds needs the whole tree: this view is truncated")
@@ -214,6 +225,13 @@ class TreeView:
 
         def walk(node, state, mover):
             """(lo, hi, move_lo, move_hi) of `node`, whose board is `state` with `mover` to move."""
+            lo, hi, mlo, mhi = walk_node(node, state, mover)
+            if per_node is not None and node.expanded:
+                for c in node.children:
+                    per_node[c.index] = (mlo[c.action], mhi[c.action])
+            return lo, hi, mlo, mhi
+
+        def walk_node(node, state, mover):
             e = int((state == 0).sum())
             entered[0] += node.expanded
             env.set_state(state)
@@ -239,6 +257,15 @@ class TreeView:
         lo, hi, mlo, mhi = walk(self.root, state, int(player))
         best = mlo.index(lo) if lo != BOUND_ILLEGAL else -1
         return dict(lo=lo, hi=hi, move_lo=mlo, move_hi=mhi, best=best, empty=int((state == 0).sum()), nodes=entered[0])
+
+    def node_bounds(self, game, board, player):
+        """score_bounds' recursion returned for every node: a list with one (move_lo, move_hi) per node of the view,
+        the bounds of the move into that node seen from its parent, (-128, -128) for the root and for an illegal
+        move.  What an arena with stored bounds keeps in the node itself (Arena.set_stored_bounds; the export's
+        move_lo / move_hi columns, TreeNode.move_lo / .move_hi), recomputed from the tree's shape alone."""
+        out = [(BOUND_ILLEGAL, BOUND_ILLEGAL)] * len(self.nodes)
+        self.score_bounds(game, board, player, per_node=out)
+        return out
 
     def render(self, max_depth=None, min_visits=1):
         """One line per node in the style of anytree's RenderTree: action, n, q, p, `#` on a node whose move
@@ -269,4 +296,7 @@ class TreeView:
                       node_n=nd.n, node_vl=nd.vl, node_w=nd.w, node_p=nd.p, player=nd.player,
                       flags=(FLAG_EXPANDED if nd.expanded else 0) | (FLAG_VALID if nd.valid else 0) |
                       (FLAG_TERMINAL if nd.terminal else 0)) for nd in self.nodes]
+        if self.has_bounds:
+            for d, nd in zip(nodes, self.nodes):
+                d.update(move_lo=nd.move_lo, move_hi=nd.move_hi)
         return dict(count=self.count, max_nodes=self.max_nodes, truncated=self.truncated, nodes=nodes)
