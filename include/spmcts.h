@@ -359,11 +359,10 @@ int spmcts_proof_stop(spmcts_arena *h, spmcts_stream stream);
 int spmcts_proof_stopped(spmcts_arena *h, int32_t *count_dev, spmcts_stream stream);
 
 /* ---- stored score bounds ---------------------------------------------------- */
-/* Solver-aware search (off by default).  `on` uint8 [T]: the trees whose search uses the stored bounds, or NULL:
- * every tree.  The first call starts the maintenance of the bounds for the whole arena (it cannot be switched off
- * again); later calls may change the use flags between launches.  THIS VERSION BUILDS THE MAINTENANCE ONLY: the
- * search rules that read the bounds during a descent are not built, so a call with any flag set (NULL included)
- * returns -2 and changes nothing, and a call with every flag 0 is how the bounds are switched on.  From that call on every
+/* The maintenance switch of the stored bounds.  `on` uint8 [T] must be all 0: the call starts the maintenance of the
+ * bounds for the whole arena (it cannot be switched off again).  A call with any flag set (NULL included) returns -2
+ * and changes nothing: which trees' searches READ the bounds is spmcts_set_solver_rules' business below, and without
+ * it no search does.  From the first call on every
  * entry j of every child block carries move_lo / move_hi of the move into child j as int8, seen from the block's
  * own node -- the values the walk of spmcts_tree_bounds_batch computes for that move -- in bytes of the node record
  * that were padding, so no layout, size or offset changes.  A new block is stamped from its board alone (a winning
@@ -371,15 +370,39 @@ int spmcts_proof_stopped(spmcts_arena *h, int32_t *count_dev, spmcts_stream stre
  * that created it then rewrites the leaf's entry in its parent's block as [-hi, -lo] of the new block and goes on
  * bottom-up along the expansion's path while an entry changes, up to the entries of the active root's children.
  * Between any two launches, mid-search included, the stored entries of every block reachable from the active root
- * equal the walk's values on the tree as it stands.  The search itself does not read them: counters, visit counts,
- * Move records and results are bit-identical with and without.  With the bounds stored, spmcts_set_proof_play's
- * verdict before a move choice, spmcts_tree_proof_moves_batch and spmcts_proof_stop read the root's block (one
- * read) and walk nothing; a root without a child block is classified from its board as before.
+ * equal the walk's values on the tree as it stands.  Without search rules the search does not read them: counters,
+ * visit counts, Move records and results are bit-identical with and without.  With the bounds stored,
+ * spmcts_set_proof_play's verdict before a move choice, spmcts_tree_proof_moves_batch and spmcts_proof_stop read the
+ * root's block (one read) and walk nothing; a root without a child block is classified from its board as before.
  * spmcts_tree_bounds_batch keeps walking: it is the independent check.
  * The first call is legal only while no tree holds more than its root block (before the first search): -4
  * otherwise.  It stamps every fresh tree's root block.  Every call synchronises.  -1: null handle; -2: a use flag
  * is set. */
 int spmcts_set_solver_search(spmcts_arena *h, const uint8_t *on);
+/* Solver-aware search (off by default): the search rules that read the stored bounds, per tree.  `rules` uint8 [T],
+ * a mask of the two bits below, or NULL: every rule off.  At a node X with `player` to move, with mlo[j] / mhi[j]
+ * the stored entries of X's child block and lo(X) their largest mlo:
+ *   SPMCTS_SOLVER_REFUTE  a child j with mhi[j] < lo(X) scores like an invalid or locked child (-1e10): it cannot
+ *                         reach what a sibling already secures.  The move that secures lo(X) is never refuted, so
+ *                         only locks can leave a select without a child (a leak, as before);
+ *   SPMCTS_SOLVER_PROVED  if the chosen child a has a child block and mlo[a] == mhi[a] = s, the sim ends there like
+ *                         a terminal one: value sign(s) * player -- for a strong_play tree and s != 0,
+ *                         (1.18 - 9 * (cells - |s| + 1) / 350.0) * sign(s) * player, what the winning move itself
+ *                         would back up -- n + 1 and w + value on the path and on a, the path's virtual loss removed.
+ *                         It counts in sims and depth_sum, not in terminal_leaves, and buys no network row.
+ * A tree without bits searches bit-identically to an arena that only stores the bounds.  The stored-bounds
+ * invariant holds with the rules on (they write no bound).  Synchronises; takes effect at the next launch.
+ * -1: null handle; -3: a bit outside the two; -4: the arena keeps no stored bounds (spmcts_set_solver_search). */
+enum { SPMCTS_SOLVER_REFUTE = 1, SPMCTS_SOLVER_PROVED = 2 };
+int spmcts_set_solver_rules(spmcts_arena *h, const uint8_t *rules);
+/* Counts since the first spmcts_set_solver_rules with a bit set, summed over the trees, int64
+ * [SPMCTS_SOLVER_NSTAT] (synchronises): [0] sims ended by SPMCTS_SOLVER_PROVED, [1] select levels at which
+ * SPMCTS_SOLVER_REFUTE removed at least one child that was otherwise valid.  All zeros before that call. */
+enum { SPMCTS_SOLVER_NSTAT = 2 };
+int spmcts_get_solver_stats(spmcts_arena *h, int64_t *out);
+/* The same per tree, int64 [T][SPMCTS_SOLVER_NSTAT] to device memory, queued on the stream with no host
+ * synchronisation. */
+int spmcts_solver_stats_trees(spmcts_arena *h, int64_t *out_dev, spmcts_stream stream);
 /* Where each tree's search stands, queued on the stream with no host synchronisation, int32 [T] each, either may be
  * NULL: started, the search_node calls the tree's current search has started (0x3fffffff: no search in progress,
  * or stopped by spmcts_proof_stop); resume, the slot its cycle goes on at * 2 + 1 if the sim cap paused it inside a

@@ -23,7 +23,9 @@ MCTreeSearch.score_bounds, TreeView.score_bounds; tree.py: bounds_to_codes, clas
 playing it (proof_play= of MCTreeSearch / SelfPlayEngine / a LeagueEngine player: Arena.set_proof_play,
 proof_moves_batch, proof_last, proof_stats, proof_stop; tree.proof_move_set, the keep set's host twin), and keeping
 the bounds in the nodes (stored_bounds= of MCTreeSearch / SelfPlayEngine: Arena.set_stored_bounds,
-Arena.export_subtrees(bounds=True), TreeView.node_bounds).
+Arena.export_subtrees(bounds=True), TreeView.node_bounds), and searching with them (solver_search= of MCTreeSearch /
+SelfPlayEngine / LanedEngine / a LeagueEngine player / analyse_positions: Arena.set_solver_rules, solver_stats;
+tree.solver_select, the two rules' host form).
 """
 from .base_model import BasePlayer, ModelContainer, Policy, TrainableModel  # noqa: F401
 from .memory import Memory  # noqa: F401
@@ -54,6 +56,7 @@ _LAZY = {
     "classify_bounds": ".tree",
     "describe_bounds": ".tree",
     "proof_move_set": ".tree",
+    "solver_select": ".tree",
     "enumerate_openings": ".openings",
     "validate_openings": ".openings",
     "SelfPlayScheduler": ".self_play_parallel",

@@ -136,6 +136,9 @@ _SIGS = {
     "spmcts_proof_stop": [_P, _P],
     "spmcts_proof_stopped": [_P, _P, _P],
     "spmcts_set_solver_search": [_P, _P],
+    "spmcts_set_solver_rules": [_P, _P],
+    "spmcts_get_solver_stats": [_P, _P],
+    "spmcts_solver_stats_trees": [_P, _P, _P],
     "spmcts_search_progress": [_P, _P, _P, _P],
     "spmcts_tree_export_bounds_batch": [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                         _P, _U64, _P],

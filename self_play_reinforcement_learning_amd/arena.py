@@ -493,7 +493,7 @@ class Arena:
         """Keep the score bounds in the nodes from now on (include/spmcts.h spmcts_set_solver_search): every child
         block carries its moves' move_lo / move_hi, stamped when the block is created and carried up the expansion's
         path, so that they equal bounds_batch's walk on the tree as it stands.  The search does not read them (its
-        results are bit-identical); the proof-play verdict, proof_moves_batch and proof_stop then read the root's
+        results are bit-identical) unless set_solver_rules says so; the proof-play verdict, proof_moves_batch and proof_stop then read the root's
         block and walk nothing, and export_subtrees(bounds=True) lists them.  Before the first search only;
         synchronises; cannot be switched off."""
         self.set_solver_search(False)
@@ -501,8 +501,9 @@ class Arena:
     def set_solver_search(self, on=False):
         """include/spmcts.h spmcts_set_solver_search: `on`, True / False for every tree or one flag per tree, says
         whose search uses the stored bounds; the first call starts their maintenance for the whole arena (before
-        the first search only).  This version builds the maintenance alone: a flag that is on raises SpmctsError
-        (-2) and changes nothing, and set_solver_search(False) is set_stored_bounds().  Synchronises."""
+        the first search only).  It is the maintenance switch alone: a flag that is on raises SpmctsError (-2) and
+        changes nothing, and set_solver_search(False) is set_stored_bounds().  The rules that read the bounds during
+        a search are switched by set_solver_rules.  Synchronises."""
         torch.cuda.current_stream().synchronize()
         if isinstance(on, (bool, int, np.bool_)):
             flags = np.full(self.n_trees, 1 if on else 0, dtype=np.uint8)
@@ -512,6 +513,52 @@ class Arena:
                 raise ValueError(f"expected {self.n_trees} per-tree entries, got {flags.shape}")
         call("spmcts_set_solver_search", self.h, flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
         self.stored_bounds = True
+
+    # ------------------------------------------------------------------ solver-aware search
+    SOLVER_REFUTE, SOLVER_PROVED = 1, 2
+    SOLVER_STATS = ("proved", "refuted_levels")
+    _solver_rules = None
+
+    @property
+    def solver_rules(self):
+        """The trees' rule bits as last set (numpy uint8 [T]; all 0 on an arena that never set any)."""
+        if self._solver_rules is None:
+            return np.zeros(self.n_trees, dtype=np.uint8)
+        return self._solver_rules
+
+    def _per_tree_bool(self, x):
+        if isinstance(x, (bool, int, np.bool_)):
+            return np.full(self.n_trees, bool(x))
+        f = np.asarray(x, dtype=bool)
+        if f.shape != (self.n_trees,):
+            raise ValueError(f"expected {self.n_trees} per-tree entries, got {f.shape}")
+        return f
+
+    def set_solver_rules(self, refute=True, proved=True):
+        """The search rules that read the stored bounds (include/spmcts.h spmcts_set_solver_rules; the host form is
+        tree.solver_select): refute, a child that cannot reach what a sibling already secures scores like an
+        invalid one; proved, a sim whose chosen child is solved ends there with the proved value and buys no row.
+        Each a bool for every tree or one flag per tree.  Off by default.  Switches the stored bounds on first if
+        they are off (before the first search only).  Synchronises; takes effect at the next launch."""
+        bits = (self._per_tree_bool(refute) * self.SOLVER_REFUTE + self._per_tree_bool(proved) * self.SOLVER_PROVED)
+        bits = np.ascontiguousarray(bits.astype(np.uint8))
+        if not self.stored_bounds:
+            self.set_stored_bounds()
+        torch.cuda.current_stream().synchronize()
+        call("spmcts_set_solver_rules", self.h, bits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+        self._solver_rules = bits
+
+    def solver_stats(self, per_tree=False):
+        """Counts of the search rules so far (spmcts_get_solver_stats; sync): proved, the sims that ended at a
+        solved child; refuted_levels, the select levels at which the refute rule removed at least one child that
+        was otherwise valid.  per_tree=True: a device int64 [T][2] tensor instead, no host sync."""
+        if per_tree:
+            out = torch.empty((self.n_trees, len(self.SOLVER_STATS)), dtype=torch.int64, device=self.device)
+            call("spmcts_solver_stats_trees", self.h, ptr(out), _stream())
+            return out
+        out = (ctypes.c_int64 * len(self.SOLVER_STATS))()
+        call("spmcts_get_solver_stats", self.h, out)
+        return dict(zip(self.SOLVER_STATS, (int(x) for x in out)))
 
     def search_progress(self):
         """Per tree, device int32 [T] each, no host sync (spmcts_search_progress): started, the search_node calls
@@ -831,6 +878,18 @@ class Arena:
         if rc != 0:
             c = self.counters()
             raise _lib.SpmctsError(f"arena device error: {_lib.describe_flags(c['error_flags'])}")
+
+
+def solver_search_rules(option):
+    """The solver_search= option of the players and engines as (refute, proved) for Arena.set_solver_rules: True both
+    rules, "refute" / "proved" one of them, False / None neither."""
+    if option is None or option is False:
+        return False, False
+    if option is True:
+        return True, True
+    if option in ("refute", "proved"):
+        return option == "refute", option == "proved"
+    raise ValueError(f'solver_search must be True, False, "refute" or "proved", got {option!r}')
 
 
 def table_net_eval(game, leaves, leaf_format, leaf_layout, salt=0, salts=None):

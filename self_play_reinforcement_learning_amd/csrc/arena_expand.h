@@ -56,7 +56,7 @@ __global__ __launch_bounds__(64) void k_expand(View v, const float *probs0, cons
   if constexpr (SB) {  // (the one expansion of this tree in the launch: nothing it reads was written here)
     int lo, hi;
     sb_stamp<G>(v, nb, blk, Board{v.lpos[tree], v.lneg[tree]}, -mover, lane, lo, hi);
-    sb_propagate<G>(v, nb, leaf, plen, lo, hi, lane, [&](int k) { return v.pnode[pb + k]; });
+    sb_propagate<G>(v, nb, leaf, plen, lo, hi, lane, [&](int k) { return v.pnode[pb + k]; }, [](bool, int, int) {});
   }
 }
 
@@ -140,10 +140,10 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
   const bool noise = v.noise_on[tree] != 0;
   const double nz = (noise && lane < G::A) ? v.noise[(size_t)tree * P + lane] : 0.0;
   TreeRng rng;
-  TreeRoot R;
+  TreeRootT<SB> R;
   if (refill) {
     rng_load(v, tree, rng);
-    R = load_root<G>(v, tree);
+    R = load_root<G, SB>(v, tree);
   }
   // the network outputs of the pending slots (second round trip: they depend on the rows)
   {
@@ -171,7 +171,7 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
     }
   }
   bool terr = false;
-  SimCnt sc;
+  SimCntT<SB> sc;
   // the cycle from the resume slot, once round (a slot met again was filled in this launch: its reply is the
   // next launch's); a searching tree cycles over its own kt slots, any other over all K (its one pending slot)
   const int kt = refill ? v.tK[tree] : K;
@@ -283,9 +283,13 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
         sf.dirty = true;
         if (plen > 0) {
           sf.fence_if_dirty();
-          if (sb_propagate<G>(v, nb, leaf, plen, lo, hi, lane, [&](int k) {
-                return k < P ? s_pnode[grp][j][k] : v.pnode[(size_t)ps * G::MAXD + k];
-              }))
+          // (a rewritten entry of the root's own block reaches TreeRoot's copy too: the fills below select on it)
+          if (sb_propagate<G>(
+                  v, nb, leaf, plen, lo, hi, lane,
+                  [&](int k) { return k < P ? s_pnode[grp][j][k] : v.pnode[(size_t)ps * G::MAXD + k]; },
+                  [&](bool me, int nlo, int nhi) {
+                    if (refill && R.rules && me) R.cbnd = sb_pack(nlo, nhi);
+                  }))
             sf.dirty = true;
         }
       }
@@ -315,7 +319,7 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
       }
     }
     if (refill) {
-      const int r = fill_slot_vl<G>(v, tree, j, limit, started, nst, R, rng, terr, pl, noise, nz, sc, sf);
+      const int r = fill_slot_vl<G, SB>(v, tree, j, limit, started, nst, R, rng, terr, pl, noise, nz, sc, sf);
       if (r == SIM_ERROR) break;  // sticky SPMCTS_ERR_STATE; counters flushed below
       if (r == SIM_PAUSED) {
         paused_at = i;
@@ -341,6 +345,9 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
   }
   if (lane == 0) {
     sc.flush(v.cnt + (size_t)tree * C_NCNT);
+    if constexpr (SB) {
+      if (sc.proved | sc.reflev) sc.flush_solver(v.sv_stats + (size_t)tree * SV_NSTAT);
+    }
   }
   if (refill && lane == 0) {
     v.tstarted[tree] = started;

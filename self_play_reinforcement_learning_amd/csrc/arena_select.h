@@ -6,6 +6,20 @@
 // (arena_solver.h, included later: the stored bounds' classification of a move from the board alone)
 template <class G>
 __device__ __forceinline__ int sb_classify(Board b, int player, int lane, int &mlo, int &mhi);
+// (arena_solver.h: the two search rules that read the stored bounds, shared by k_select and sim_vl)
+template <int P>
+__device__ __forceinline__ bool sb_refuted(int mlo, int mhi);
+__device__ __forceinline__ bool sb_proved(int cc, int mlo, int mhi);
+template <class G>
+__device__ __forceinline__ double sb_proved_value(bool strong, int s, int player);
+__device__ __forceinline__ int sb_pack(int mlo, int mhi);
+__device__ __forceinline__ int sb_lo(int packed);
+__device__ __forceinline__ int sb_hi(int packed);
+enum { SB_NONE = -128 };  // an illegal move or a pad lane: arena_tree.h's TB_NONE (bounds_root asserts they agree)
+// rule bits of a tree (View::sv_rules, spmcts_set_solver_rules) and its two statistics (View::sv_stats)
+enum { SBR_REFUTE = 1, SBR_PROVED = 2 };
+enum { SV_PROVED = 0, SV_REFLEV = 1, SV_NSTAT = 2 };
+__device__ __forceinline__ int sb_rules(const View &v, int tree) { return v.sv_rules ? (int)v.sv_rules[tree] : 0; }
 
 // SB (arena_solver.h): the root block is stamped with the empty board's stored bounds.
 template <class G, bool SB = false>
@@ -351,6 +365,33 @@ __device__ __forceinline__ void group_argmax_carry(double &s, int &idx, int &c0,
   if constexpr (P == 16) argmax_carry_step<DPP_MIRROR>(s, idx, c0, c1, c2, d0);
 }
 
+// the same with a fourth int payload (the SB = true selects carry the winner's stored bounds).  A copy on purpose,
+// not a variadic payload under both: the SB = false kernels keep calling group_argmax_carry as it stood, so their
+// code stays the parent's instruction for instruction; a change to the comparison must be made in both
+template <int CTRL>
+__device__ __forceinline__ void argmax_carry4_step(double &s, int &idx, int &c0, int &c1, int &c2, int &c3, double &d0) {
+  const double so = dpp_d<CTRL>(s), d0o = dpp_d<CTRL>(d0);
+  const int io = dpp_i<CTRL>(idx), c0o = dpp_i<CTRL>(c0), c1o = dpp_i<CTRL>(c1), c2o = dpp_i<CTRL>(c2);
+  const int c3o = dpp_i<CTRL>(c3);
+  if (so > s || (so == s && io < idx)) {
+    s = so;
+    idx = io;
+    c0 = c0o;
+    c1 = c1o;
+    c2 = c2o;
+    c3 = c3o;
+    d0 = d0o;
+  }
+}
+template <int P>
+__device__ __forceinline__ void group_argmax_carry4(double &s, int &idx, int &c0, int &c1, int &c2, int &c3, double &d0) {
+  static_assert(P == 8 || P == 16, "tree groups of 8 or 16 lanes");
+  argmax_carry4_step<DPP_XOR1>(s, idx, c0, c1, c2, c3, d0);
+  argmax_carry4_step<DPP_XOR2>(s, idx, c0, c1, c2, c3, d0);
+  argmax_carry4_step<DPP_HALF_MIRROR>(s, idx, c0, c1, c2, c3, d0);
+  if constexpr (P == 16) argmax_carry4_step<DPP_MIRROR>(s, idx, c0, c1, c2, c3, d0);
+}
+
 template <int P>
 __device__ __forceinline__ int group_or(int x) {
   static_assert(P == 8 || P == 16, "tree groups of 8 or 16 lanes");
@@ -361,7 +402,10 @@ __device__ __forceinline__ int group_or(int x) {
   return x;
 }
 
-template <class G>
+// SB (arena_solver.h "Solver-aware search"): the level's stored bounds are loaded with its other child fields, and
+// behind the tree's rule bits a refuted child scores like an invalid one (R1) and a sim whose chosen child is
+// solved ends there like a terminal one (R2).
+template <class G, bool SB = false>
 __global__ __launch_bounds__(64) void k_select(View v, int n_active) {
   constexpr int P = G::APAD;
   constexpr int GPB = 64 / P;  // groups (trees) per block
@@ -387,6 +431,8 @@ __global__ __launch_bounds__(64) void k_select(View v, int n_active) {
   TreeRng rng;
   rng_load(v, tree, rng);
   bool terr = false;
+  int rules = 0, reflev = 0;  // SB: the tree's rule bits, the levels of this sim at which R1 removed a child
+  if constexpr (SB) rules = sb_rules(v, tree);
 
   int node_n = nd_n<P>(v, nb + node);
   double node_w = nd_w<P>(v, nb + node);
@@ -415,11 +461,26 @@ __global__ __launch_bounds__(64) void k_select(View v, int n_active) {
       cp = nd_p<P>(v, ci);
       cc = nd_c<P>(v, ci);
     }
+    int mlo = SB_NONE, mhi = SB_NONE;
+    if constexpr (SB) {
+      if (rules && lane < G::A) {
+        mlo = nd_lo<P>(v, ci);
+        mhi = nd_hi<P>(v, ci);
+      }
+    }
     const int gbase = (threadIdx.x & 63) & ~(P - 1);
     // the jitter does not depend on the child block: drawn here, it overlaps the loads above
     bool terr_j = false;
     const double jit = rng_group<G>(v, rng, lane, gbase, &terr_j);
-    const bool valid = (lane < G::A) && ((vm >> lane) & 1u);
+    bool valid = (lane < G::A) && ((vm >> lane) & 1u);
+    if constexpr (SB) {
+      if (rules & SBR_REFUTE) {  // R1: the move cannot reach what a sibling already secures
+        const bool cut = sb_refuted<P>(mlo, mhi);  // (a group maximum: every lane calls it)
+        const bool ref = valid && cut;
+        reflev += group_or<P>(ref ? 1 : 0);
+        valid = valid && !ref;
+      }
+    }
     double score = -10000000000.0;  // mcts.py:347
     if (valid) {
       // q (mcts.py:59-62): children carry no virtual loss in sequential mode
@@ -446,20 +507,36 @@ __global__ __launch_bounds__(64) void k_select(View v, int n_active) {
     const int cn_a = __shfl(cn, gbase + a, 64);
     const double cw_a = __shfl(cw, gbase + a, 64);
     const int child = cb * P + a;
-    if (cc_a < 0) {
+    bool proved = false;  // R2: the chosen child is solved, the sim ends here with the proved value
+    int s_a = 0;
+    if constexpr (SB) {
+      if (rules & SBR_PROVED) {
+        s_a = __shfl(mlo, gbase + a, 64);
+        proved = sb_proved(cc_a, s_a, __shfl(mhi, gbase + a, 64));
+      }
+    }
+    if (cc_a < 0 || proved) {
       // leaf reached: _expand_node (mcts.py:301-321)
       Board nb2 = b;
       int rew = 0, done = 0;
-      const int st = step<G>(nb2, a, player, &rew, &done);
+      int st = STEP_OK;
+      if (!proved)
+        st = step<G>(nb2, a, player, &rew, &done);
+      else
+        done = 1;
       if (lane == 0) {
         if (st != STEP_OK) set_err(v, SPMCTS_ERR_STATE);
         int64_t *cnt = v.cnt + (size_t)tree * C_NCNT;
         cnt[C_SIMS] += 1;
         cnt[C_DEPTH] += depth + 1;
+        if constexpr (SB) {
+          if (proved) v.sv_stats[(size_t)tree * SV_NSTAT + SV_PROVED] += 1;
+          if (reflev) v.sv_stats[(size_t)tree * SV_NSTAT + SV_REFLEV] += reflev;
+        }
         if (done) {
           // terminal: value r (or strong_play shaping), no children, backup in place
-          const double val = terminal_value(v, tree, b, rew * player);
           const bool strong = v.tstrong[tree] != 0;
+          const double val = proved ? sb_proved_value<G>(strong, s_a, player) : terminal_value(v, tree, b, rew * player);
           for (int k = 0; k <= depth; ++k) {
             const size_t idx = nb + s_node[grp][k];
             nd_n<P>(v, idx) = s_n[grp][k] + 1;
@@ -469,7 +546,7 @@ __global__ __launch_bounds__(64) void k_select(View v, int n_active) {
           nd_n<P>(v, nb + child) = cn_a + 1;
           nd_w<P>(v, nb + child) = cw_a + val;
           if (strong) nd_f<P>(v, nb + child) = 1;
-          cnt[C_TERM] += 1;
+          if (!proved) cnt[C_TERM] += 1;
         } else {
           // pending network evaluation: stash the path for k_expand
           const size_t pb = (size_t)tree * G::MAXD;
@@ -566,12 +643,20 @@ struct TreeRoot {
   float cp;
   uint32_t vm;
 };
+// The root of the SB = true kernels: also the tree's rule bits and, while any is set, the stored bounds of the
+// root's child block (lane j < A: sb_pack of entry j).  An sb_propagate that rewrites an entry of that block
+// updates the copy too (expand_vl_body interleaves replies and fills in one launch).
+struct TreeRootSB : TreeRoot {
+  int rules, cbnd;
+};
+template <bool SB>
+using TreeRootT = std::conditional_t<SB, TreeRootSB, TreeRoot>;
 
-template <class G>
-__device__ __forceinline__ TreeRoot load_root(const View &v, int tree) {
+template <class G, bool SB = false>
+__device__ __forceinline__ TreeRootT<SB> load_root(const View &v, int tree) {
   constexpr int P = G::APAD;
   const size_t nb = nbase<G>(v, tree);
-  TreeRoot R;
+  TreeRootT<SB> R;
   R.strong = v.tstrong[tree] != 0;
   R.node = v.root[tree];
   R.b = Board{v.rpos[tree], v.rneg[tree]};
@@ -587,6 +672,10 @@ __device__ __forceinline__ TreeRoot load_root(const View &v, int tree) {
   R.cw = 0.0;
   R.cp = 0.f;
   R.vm = 0u;
+  if constexpr (SB) {
+    R.rules = sb_rules(v, tree);
+    R.cbnd = sb_pack(SB_NONE, SB_NONE);
+  }
   if (R.cb >= 0) {
     R.vm = nd_vm<P>(v, (size_t)tree * v.cap + R.cb);
     if (lane < G::A) {
@@ -596,6 +685,9 @@ __device__ __forceinline__ TreeRoot load_root(const View &v, int tree) {
       R.cp = nd_p<P>(v, ci);
       R.cc = nd_c<P>(v, ci);
       R.cvl = nd_vl<P>(v, ci);
+      if constexpr (SB) {
+        if (R.rules) R.cbnd = sb_pack(nd_lo<P>(v, ci), nd_hi<P>(v, ci));
+      }
     }
   }
   return R;
@@ -645,6 +737,19 @@ struct SimCnt {
   }
 };
 
+// The counters of the SB = true kernels: also the two statistics of the search rules (View::sv_stats) -- sims ended
+// by R2, select levels at which R1 removed a child.  Only a tree with a rule bit set counts any, and its arena has
+// the array (spmcts_set_solver_rules).
+struct SimCntSB : SimCnt {
+  int64_t proved = 0, reflev = 0;
+  __device__ void flush_solver(int64_t *st) const {
+    if (proved) st[SV_PROVED] += proved;
+    if (reflev) st[SV_REFLEV] += reflev;
+  }
+};
+template <bool SB>
+using SimCntT = std::conditional_t<SB, SimCntSB, SimCnt>;
+
 // One search_node with virtual loss (mcts.py:340-367) for pending slot j of `tree`, run by the
 // tree's P-lane group.  vl += 1 on every node passed (mcts.py:345), children scored with
 // q = (w - vl)/(n + vl) and u = c p sqrt(N + vl_parent)/(1 + n + vl) (mcts.py:59-78), pending leaves
@@ -652,9 +757,11 @@ struct SimCnt {
 // locked and its path stashed in slot j, SIM_DONE for a terminal leaf (backed up, path vl removed),
 // SIM_LEAK for a leak, SIM_ERROR on a corrupt tree; R (the root in registers) is updated to match and sf
 // records the stores issued.  The return value is uniform across the group.
-template <class G>
-__device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng, bool &terr, const PathLds &pl,
-                      bool noise, double nz, SimCnt &sc, StoreFence &sf) {
+// SB (arena_solver.h "Solver-aware search"): the level's stored bounds come with its other child fields (the root's
+// block from R), and R1 / R2 apply behind the tree's rule bits; an R2 end is the terminal branch with the proved value.
+template <class G, bool SB = false>
+__device__ int sim_vl(const View &v, int tree, int j, TreeRootT<SB> &R, TreeRng &rng, bool &terr, const PathLds &pl,
+                      bool noise, double nz, SimCntT<SB> &sc, StoreFence &sf) {
   constexpr int P = G::APAD;
   const int lane = threadIdx.x & (P - 1);
   const int gbase = (threadIdx.x & 63) & ~(P - 1);
@@ -694,6 +801,7 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
     double cw = 0.0;
     float cp = 0.f;
     int lcs = kRootRegs;  // where this level's child block (cb) sits
+    int bnd = 0;          // SB with a rule on: sb_pack of this lane's stored entry
     if (depth == 0) {  // the root's child block, from registers
       vm = R.vm;
       cn = R.cn;
@@ -701,6 +809,7 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
       cp = R.cp;
       cc = R.cc;
       cvl = R.cvl;
+      if constexpr (SB) bnd = R.cbnd;
     } else {
       lcs = kUncached;
       sf.fence_if_dirty();
@@ -713,12 +822,24 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
         cc = nd_c<P>(v, ci);
         cvl = nd_vl<P>(v, ci);
       }
+      if constexpr (SB) {
+        bnd = sb_pack(SB_NONE, SB_NONE);
+        if (R.rules && lane < G::A) bnd = sb_pack(nd_lo<P>(v, ci), nd_hi<P>(v, ci));
+      }
     }
     // the jitter does not depend on the child block: drawn here, it overlaps the loads above
     bool terr_j = false;
     const double jit = rng_group<G>(v, rng, lane, gbase, &terr_j);
     // valid (mcts.py:86-88): valid move and not locked by a pending sim
-    const bool valid = (lane < G::A) && ((vm >> lane) & 1u) && cc != -2;
+    bool ref = false;  // R1: the move cannot reach what a sibling already secures
+    if constexpr (SB) {
+      if (R.rules & SBR_REFUTE) {
+        const bool cut = sb_refuted<P>(sb_lo(bnd), sb_hi(bnd));  // (a group maximum: every lane calls it)
+        ref = cut && (lane < G::A) && ((vm >> lane) & 1u) && cc != -2;
+        sc.reflev += group_or<P>(ref ? 1 : 0);
+      }
+    }
+    const bool valid = (lane < G::A) && ((vm >> lane) & 1u) && cc != -2 && !ref;
     double score = -10000000000.0;
     if (valid) {
       // q (mcts.py:59-62): (w - vl) / (n + vl)
@@ -746,17 +867,29 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
     int a = lane;
     int cc_a = cc, cn_a = cn, cvl_a = cvl;
     double cw_a = cw;
-    group_argmax_carry<P>(s, a, cc_a, cn_a, cvl_a, cw_a);  // lane a's child fields in every lane
+    bool proved = false;  // R2: the chosen child is solved, the sim ends here with the proved value
+    int bnd_a = bnd;
+    if constexpr (SB) {
+      group_argmax_carry4<P>(s, a, cc_a, cn_a, cvl_a, bnd_a, cw_a);  // ... and its stored entry
+      proved = (R.rules & SBR_PROVED) && sb_proved(cc_a, sb_lo(bnd_a), sb_hi(bnd_a));
+    } else {
+      group_argmax_carry<P>(s, a, cc_a, cn_a, cvl_a, cw_a);  // lane a's child fields in every lane
+    }
     const int child = cb * P + a;
-    if (cc_a < 0) {
+    if (cc_a < 0 || proved) {
       // leaf: _expand_node (mcts.py:301-321)
       Board nb2 = b;
       int rew = 0, done = 0;
-      const int st = step<G>(nb2, a, player, &rew, &done);
+      int st = STEP_OK;
+      if (!proved)
+        st = step<G>(nb2, a, player, &rew, &done);
+      else
+        done = 1;
       if (done) {
         // terminal: backup (mcts.py:94-98) then remove the path's virtual loss (:365); one lane per
         // path node, the values this sim read (pl: written by lane 0 of this wave, LDS stays in order)
-        const double val = terminal_value(R.strong, b, rew * player);
+        const double val =
+            proved ? sb_proved_value<G>(R.strong, sb_lo(bnd_a), player) : terminal_value(R.strong, b, rew * player);
         const bool strong = R.strong;
         int unc = 0;
         for (int k = lane; k <= depth; k += P) {
@@ -788,7 +921,8 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
           R.cn += 1;
           R.cw += val;
         }
-        sc.term += 1;
+        if constexpr (SB) sc.proved += proved ? 1 : 0;
+        if (!proved) sc.term += 1;
       } else {
         const size_t pb = (size_t)ps * G::MAXD;
         int unc = 0;
@@ -841,15 +975,15 @@ __device__ int sim_vl(const View &v, int tree, int j, TreeRoot &R, TreeRng &rng,
 // started View::simcap sims of this tree (`nst` counts them; SIM_PAUSED, before a sim and never in one).  No fence
 // between sims: a sim reads the root and its children from the registers, and StoreFence's `dirty` rule fences
 // before any global read of node records after a store to one.
-template <class G>
-__device__ int fill_slot_vl(const View &v, int tree, int j, int limit, int &started, int &nst, TreeRoot &R,
-                            TreeRng &rng, bool &terr, const PathLds &pl, bool noise, double nz, SimCnt &sc,
+template <class G, bool SB = false>
+__device__ int fill_slot_vl(const View &v, int tree, int j, int limit, int &started, int &nst, TreeRootT<SB> &R,
+                            TreeRng &rng, bool &terr, const PathLds &pl, bool noise, double nz, SimCntT<SB> &sc,
                             StoreFence &sf) {
   while (started < limit) {
     if (v.simcap && nst >= v.simcap) return SIM_PAUSED;
     ++started;
     ++nst;
-    const int r = sim_vl<G>(v, tree, j, R, rng, terr, pl, noise, nz, sc, sf);
+    const int r = sim_vl<G, SB>(v, tree, j, R, rng, terr, pl, noise, nz, sc, sf);
     if (r == SIM_PENDING || r == SIM_ERROR) return r;
   }
   return SIM_DONE;

@@ -15,7 +15,7 @@
 // Only the kernels of the stored-bounds set (the SB = true instantiations, launched once spmcts_set_solver_search
 // switched maintenance on) call any of this; the SB = false kernels never touch the two arrays.
 
-enum { SB_NONE = -128 };  // an illegal move or a pad lane: arena_tree.h's TB_NONE (bounds_root asserts they agree)
+// (SB_NONE = -128, an illegal move or a pad lane, is declared with the rules' forward declarations in arena_select.h)
 
 // the largest x of the group, in every lane (arena_tree.h's group_max is this function)
 template <int P>
@@ -26,6 +26,37 @@ __device__ __forceinline__ int sb_group_max(int x) {
   x = max(x, dpp_i<DPP_HALF_MIRROR>(x));
   if constexpr (P == 16) x = max(x, dpp_i<DPP_MIRROR>(x));
   return x;
+}
+
+// ---- the search rules (DESIGN.md §4 "Solver-aware search"; k_select and sim_vl behind the tree's rule bits) ----
+// A lane's stored entry in one register: lo in bits 0..7, hi in bits 8..15 (TreeRoot keeps the root block's).
+__device__ __forceinline__ int sb_pack(int mlo, int mhi) { return (mlo & 0xff) | ((mhi & 0xff) << 8); }
+__device__ __forceinline__ int sb_lo(int packed) { return (int)(int8_t)(packed & 0xff); }
+__device__ __forceinline__ int sb_hi(int packed) { return (int)(int8_t)((packed >> 8) & 0xff); }
+
+// R1, refute: this lane's move cannot reach lo(X) = the most a sibling already secures.  Every lane of the group
+// calls it (a group maximum); an illegal move and a pad lane hold SB_NONE and are "refuted" too, which their
+// callers never see (they are invalid already).  The move that secures lo(X) has mhi >= mlo == lo(X): it stays.
+template <int P>
+__device__ __forceinline__ bool sb_refuted(int mlo, int mhi) {
+  return mhi < sb_group_max<P>(mlo);
+}
+
+// R2, proved end: the chosen child has a block of its own and its score is known exactly.  (A terminal move has no
+// block and keeps its own path; an open move without a block has mlo < mhi; a locked child has no block.)
+__device__ __forceinline__ bool sb_proved(int cc, int mlo, int mhi) { return cc >= 0 && mlo == mhi; }
+
+// The value an R2 end backs up, for the node's `player` and the child's exact score s seen from that player: the
+// sign of s for the player, shaped for a strong_play tree as terminal_value shapes the winning move itself -- the
+// score is the number of empty cells where that move is played, so np.sum(np.abs(state)) + 1 there is CELLS - |s| + 1.
+template <class G>
+__device__ __forceinline__ double sb_proved_value(bool strong, int s, int player) {
+  const int r = (s > 0 ? 1 : (s < 0 ? -1 : 0)) * player;
+  if (strong && s != 0) {
+    const int num_steps = G::CELLS - (s > 0 ? s : -s) + 1;
+    return (1.18 - ((double)(9 * num_steps) / 350.0)) * (double)r;
+  }
+  return (double)r;
 }
 
 // Lane j's move at a node (board b, `player` to move), from the board alone: legal iff step accepts it and places
@@ -77,10 +108,12 @@ __device__ __forceinline__ void sb_stamp(const View &v, size_t nb, int blk, Boar
 // recomputes the parent's bounds from its block and rewrites the parent's entry in the block above, up to the
 // entries of the active root's children.  plen == 0 (the new block is the active root's own): nothing to write.
 // Every lane of the group takes the same branches.  Returns whether any entry was written; the caller orders these
-// stores before later reads of the same words (one wave owns the tree).
-template <class G, class PathF>
+// stores before later reads of the same words (one wave owns the tree).  on_root(me, nlo, nhi) runs in every lane
+// when the walk rewrites an entry of the active root's own child block (`me`: this lane holds that entry): a launch
+// that keeps that block in registers (TreeRoot) updates its copy there.
+template <class G, class PathF, class RootF>
 __device__ __forceinline__ bool sb_propagate(const View &v, size_t nb, int leaf, int plen, int lo, int hi, int lane,
-                                             PathF path) {
+                                             PathF path, RootF on_root) {
   constexpr int P = G::APAD;
   bool wrote = false;
   int node = leaf;
@@ -97,7 +130,10 @@ __device__ __forceinline__ bool sb_propagate(const View &v, size_t nb, int leaf,
       mhi = nhi;
     }
     wrote = true;
-    if (k == 0) break;  // the parent is the active root
+    if (k == 0) {  // the parent is the active root
+      on_root(me, nlo, nhi);
+      break;
+    }
     lo = sb_group_max<P>(mlo);
     hi = sb_group_max<P>(mhi);
     node = path(k);

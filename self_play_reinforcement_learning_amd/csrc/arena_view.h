@@ -151,6 +151,11 @@ struct View {
   int8_t *pf_lo, *pf_hi;
   unsigned long long *pf_stats;
   int32_t *pf_nstop;
+  // solver-aware search (spmcts_set_solver_rules, arena_solver.h; null until first use): sv_rules uint8 [T], the
+  // search rules each tree's selects apply to the stored bounds (SBR_REFUTE | SBR_PROVED; null again while every
+  // tree has none); sv_stats int64 [T][SV_NSTAT], sims ended by R2 and select levels at which R1 removed a child
+  uint8_t *sv_rules;
+  int64_t *sv_stats;
 };
 
 enum : uint32_t { PF_ALL = 0xffffffffu };

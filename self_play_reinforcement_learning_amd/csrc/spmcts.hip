@@ -57,6 +57,7 @@
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "board.h"
@@ -155,6 +156,8 @@ struct spmcts_arena {
   // stored score bounds (spmcts_set_solver_search, arena_solver.h): the arena launches the SB = true kernels
   // (LAUNCH_SB below), the resets' among them
   bool sb = false;
+  // solver-aware search (spmcts_set_solver_rules): the rule bits' and the statistics' allocations (View::sv_*)
+  std::vector<void *> solver_allocs;
 };
 
 static bool league_on(const spmcts_arena *h) { return h->lg.n > 0; }
@@ -523,6 +526,7 @@ int spmcts_arena_destroy(spmcts_arena *h) {
   if (h->nm_alloc) (void)hipFree(h->nm_alloc);
   for (void *p : h->log_allocs) (void)hipFree(p);
   for (void *p : h->proof_allocs) (void)hipFree(p);
+  for (void *p : h->solver_allocs) (void)hipFree(p);
   delete h;
   return 0;
 }
@@ -709,7 +713,7 @@ int spmcts_select_tree(spmcts_arena *h, spmcts_stream stream) {
     const long long lanes = (long long)n * h->P;
     View dv = h->v;  // k_select_vl walks the active list as a packed domain
     set_domain(h, dv, true);
-    rc = h->v.K > 1 ? LAUNCH_SB(h, k_select_vl, lanes, SELECT_THREADS, s, dv) : LAUNCH(h, k_select, lanes, 64, s, h->v, n);
+    rc = h->v.K > 1 ? LAUNCH_SB(h, k_select_vl, lanes, SELECT_THREADS, s, dv) : LAUNCH_SB(h, k_select, lanes, 64, s, h->v, n);
   }
   h->v.sim += h->v.K;
   return rc;
@@ -1393,7 +1397,8 @@ int spmcts_set_solver_search(spmcts_arena *h, const uint8_t *on) {
   if (!h) return fail(-1, "null arena");
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipDeviceSynchronize());
-  // the use flags: the search rules that read the stored bounds are not built, so no tree can use them yet
+  // the use flags stay refused here: the search rules that read the stored bounds are switched per tree by
+  // spmcts_set_solver_rules, and this call remains the maintenance switch
   bool any = !on;
   if (on)
     for (int t = 0; t < h->v.T; ++t) any |= on[t] != 0;
@@ -1412,6 +1417,71 @@ int spmcts_set_solver_search(spmcts_arena *h, const uint8_t *on) {
     return rc;
   }
   HIP_TRY(hipDeviceSynchronize());
+  return 0;
+}
+
+// ---- solver-aware search -----------------------------------------------------
+int spmcts_set_solver_rules(spmcts_arena *h, const uint8_t *rules) {
+  if (!h) return fail(-1, "null arena");
+  static_assert(SPMCTS_SOLVER_REFUTE == SBR_REFUTE && SPMCTS_SOLVER_PROVED == SBR_PROVED, "rule bits");
+  const size_t T = h->v.T;
+  bool any = false;
+  if (rules)
+    for (size_t t = 0; t < T; ++t) {
+      if (rules[t] & ~(SPMCTS_SOLVER_REFUTE | SPMCTS_SOLVER_PROVED))
+        return fail(-3, "solver rules: a bit outside SPMCTS_SOLVER_REFUTE | SPMCTS_SOLVER_PROVED");
+      any |= rules[t] != 0;
+    }
+  if (!h->sb) return fail(-4, "the arena keeps no stored bounds (spmcts_set_solver_search)");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (!any && h->solver_allocs.empty()) return 0;  // never on: nothing to switch off
+  const size_t bytes[2] = {T, 8 * (size_t)SV_NSTAT * T};
+  if (h->solver_allocs.empty()) {
+    void *p[2] = {};
+    for (int i = 0; i < 2; ++i) {
+      hipError_t e = hipMalloc(&p[i], bytes[i]);
+      if (e == hipSuccess) e = hipMemset(p[i], 0, bytes[i]);
+      if (e != hipSuccess) {
+        for (int j = 0; j <= i; ++j)
+          if (p[j]) (void)hipFree(p[j]);
+        return fail(-1000 - (int)e, std::string("solver rules hipMalloc: ") + hipGetErrorString(e));
+      }
+    }
+    h->solver_allocs.assign(p, p + 2);
+  }
+  if (any) {
+    HIP_TRY(hipMemcpy(h->solver_allocs[0], rules, T, hipMemcpyHostToDevice));
+  } else {
+    HIP_TRY(hipMemset(h->solver_allocs[0], 0, T));
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  h->v.sv_rules = any ? (uint8_t *)h->solver_allocs[0] : nullptr;
+  h->v.sv_stats = (int64_t *)h->solver_allocs[1];
+  return 0;
+}
+
+int spmcts_get_solver_stats(spmcts_arena *h, int64_t *out) {
+  if (!h || !out) return fail(-1, "null argument");
+  static_assert(SPMCTS_SOLVER_NSTAT == SV_NSTAT, "solver stats layout");
+  for (int i = 0; i < SV_NSTAT; ++i) out[i] = 0;
+  if (h->solver_allocs.empty()) return 0;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<int64_t> st((size_t)SV_NSTAT * h->v.T);
+  HIP_TRY(hipMemcpy(st.data(), h->solver_allocs[1], 8 * st.size(), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < st.size(); ++i) out[i % SV_NSTAT] += st[i];
+  return 0;
+}
+
+int spmcts_solver_stats_trees(spmcts_arena *h, int64_t *out_dev, spmcts_stream stream) {
+  if (!h || !out_dev) return fail(-1, "null argument");
+  const size_t bytes = 8 * (size_t)SV_NSTAT * h->v.T;
+  if (h->solver_allocs.empty()) {
+    HIP_TRY(hipMemsetAsync(out_dev, 0, bytes, (hipStream_t)stream));
+  } else {
+    HIP_TRY(hipMemcpyAsync(out_dev, h->solver_allocs[1], bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  }
   return 0;
 }
 

@@ -311,7 +311,9 @@ class Elo:
                 kw = e["policy_kwargs"]
                 out.append(dict(network=self.model_database.network(name), iterations=int(kw.get("iterations", 100)),
                                 alpha=float(kw.get("alpha", 1)), strong_play=bool(kw.get("strong_play", False)),
-                                search_threads=self.search_threads, proof_play=bool(kw.get("proof_play", False))))
+                                search_threads=self.search_threads, proof_play=bool(kw.get("proof_play", False)),
+                                solver_search=kw.get("solver_search", False),
+                                stored_bounds=bool(kw.get("stored_bounds", False))))
             elif e["policy"] == "Negamax":
                 out.append(dict(kind="negamax", depth=int(e["policy_kwargs"].get("depth", 2))))
             else:
@@ -343,9 +345,12 @@ class Elo:
             raise ValueError("compare_models needs at least two different models")
         pairings = list(itertools.combinations(range(len(names)), 2))
         game = game_of_env(self.model_database.env)
-        eng = LeagueEngine(game, self.named_players(names), pairings, games_per_pairing=num_games,
+        players = self.named_players(names)
+        eng = LeagueEngine(game, players, pairings, games_per_pairing=num_games,
                            seed=self.seed + 7919 * self.calls, search_threads=self.search_threads, dtype=self.dtype,
-                           device=self.device, openings=parse_openings(openings, game), record_games=record_games)
+                           device=self.device, openings=parse_openings(openings, game), record_games=record_games,
+                           # (kept for the whole arena: any model's stored_bounds switches them on)
+                           stored_bounds=any(p.get("stored_bounds") for p in players))
         self.calls += 1
         try:
             breakdowns = eng.play()
@@ -413,7 +418,8 @@ class Elo:
             out("")
         return records
 
-    def analyse(self, name, moves, pv_len=8, tree_depth=2, min_visits=2, out=None, bounds=False, kept_moves=False):
+    def analyse(self, name, moves, pv_len=8, tree_depth=2, min_visits=2, out=None, bounds=False, kept_moves=False,
+                solver_search=None):
         """One registered MCTreeSearch model's search of the position after `moves` (a move list from the empty
         board): mcts.analyse_positions with the model's own iterations / alpha / strong_play, its principal
         variation of at most pv_len moves and its tree to tree_depth (nodes with at least min_visits visits).
@@ -422,7 +428,9 @@ class Elo:
         search's tree has proved about the position (Arena.bounds_batch; analyse_positions' bound_* keys) and one
         more line of text, e.g. "proved: win in 5 by 3" or "bounds: at least a draw" (tree.describe_bounds).
         kept_moves=True (with bounds) appends the moves proof-guided play would choose among to that line,
-        "proved: win in 5 by 3; keeps 3" (analyse_positions' keep; tree.describe_proof_moves)."""
+        "proved: win in 5 by 3; keeps 3" (analyse_positions' keep; tree.describe_proof_moves).  solver_search: True |
+        "refute" | "proved" searches with the stored bounds (Arena.set_solver_rules) and adds a line with the rules'
+        counts; None = the model's own policy_kwargs["solver_search"]."""
         from .arena import game_of_env
         from .mcts import analyse_positions
         from .tree import TreeView, describe_bounds, describe_proof_moves
@@ -437,7 +445,8 @@ class Elo:
                                 search_threads=self.search_threads, seed=self.seed, alpha=float(kw.get("alpha", 1)),
                                 strong_play=bool(kw.get("strong_play", False)), device=self.device, dtype=self.dtype,
                                 pv_len=int(pv_len), tree=dict(max_nodes=2 + its, min_visits=int(min_visits),
-                                                              max_depth=tree_depth), bounds=bool(bounds))
+                                                              max_depth=tree_depth), bounds=bool(bounds),
+                                solver_search=kw.get("solver_search", False) if solver_search is None else solver_search)
         view = TreeView.from_export(res["tree"], 0)
         cn, cw, cp = (res[k][0].cpu().numpy() for k in ("child_n", "child_w", "child_p"))
         lines = [f"{name}: {its} simulations after moves {list(moves)}; root n={int(res['root_n'][0])} "
@@ -460,6 +469,10 @@ class Elo:
                                          int(res["bound_best"][0])))
             if kept_moves:
                 lines[-1] += "; " + describe_proof_moves(int(res["keep"][0]) & 0xffffffff)
+        if "solver_stats" in res:
+            st = res["solver_stats"]
+            lines.append(f"solver search: {st['proved']} sims ended at a proved child, "
+                         f"{st['refuted_levels']} select levels refuted a child")
         res = dict(res, view=view, text="\n".join(lines))
         if out is not None:
             out(res["text"])
@@ -518,6 +531,8 @@ def main(argv=None):
     parser.add_argument("--min-visits", type=int, default=2, help="analyse: fewest visits of a node shown")
     parser.add_argument("--bounds", action="store_true",
                         help="analyse: add what the search's tree has proved about the position")
+    parser.add_argument("--solver-search", action="store_true",
+                        help="analyse: search with the stored score bounds (refuted children, proved sims)")
     parser.add_argument("--kept-moves", action="store_true",
                         help="analyse --bounds: add the moves proof-guided play would choose among to that line")
     args = parser.parse_args(argv)
@@ -535,7 +550,8 @@ def main(argv=None):
         if not args.p or len(args.p) != 1:
             parser.error("analyse needs --p with one model name")
         elo.analyse(args.p[0], args.moves, pv_len=args.pv, tree_depth=args.tree_depth, min_visits=args.min_visits,
-                    out=print, bounds=args.bounds, kept_moves=args.kept_moves)
+                    out=print, bounds=args.bounds, kept_moves=args.kept_moves,
+                    solver_search=True if args.solver_search else None)
     else:
         names = args.p or list(elo.model_database.models().keys())
         print(json.dumps(elo.compare_models(*names, num_games=args.games, openings=args.openings,

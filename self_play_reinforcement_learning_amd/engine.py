@@ -34,7 +34,7 @@ import time
 import torch
 
 from . import _lib, distributed
-from .arena import Arena
+from .arena import Arena, solver_search_rules
 from .evaluator import make_evaluator
 from .openings import validate_openings
 
@@ -103,9 +103,13 @@ class SelfPlayEngine:
                  opponent_iterations=None, record=True, search_threads=1, leaf_dedup=None, opponent_alpha=None,
                  opponent_strong_play=None, opponent_search_threads=None, eval_cache=None, openings=None,
                  opening_period=0, opponent_depth=2, record_games=False, proof_play=False, opponent_proof_play=None,
-                 proof_stop_every=0, stored_bounds=False):
+                 proof_stop_every=0, stored_bounds=False, solver_search=False, opponent_solver_search=None):
         """stored_bounds: keep the score bounds in the nodes (Arena.set_stored_bounds; off by default): games are
         bit-identical, and the proof_play verdict and proof_stop read the root's block instead of walking the tree.
+        solver_search: True | "refute" | "proved" | False (the default), the policy's selects read the stored bounds
+        (Arena.set_solver_rules; stored bounds come with it): a child proved worse than what a sibling secures draws
+        no sims, a sim that reaches a solved child ends there without a network row; opponent_solver_search: the
+        same for the opposing MCTS side, None = the policy's.  Other games than without it.
         proof_play: the policy's move choice uses what its tree has proved (Arena.set_proof_play; off by
         default); opponent_proof_play: the same for the opposing MCTS side, None = the policy's (a hard-coded
         opponent is unaffected either way).  proof_stop_every=N > 0: after every N-th simulation step of a ply a
@@ -210,6 +214,13 @@ class SelfPlayEngine:
         self.stored_bounds = bool(stored_bounds)
         if self.stored_bounds:  # (no game has started: every tree holds its root block at most)
             self.arena.set_stored_bounds()
+        self.solver_search = solver_search
+        rules = [solver_search_rules(solver_search),
+                 solver_search_rules(solver_search if opponent_solver_search is None else opponent_solver_search)]
+        if any(any(r) for r in rules):  # tree 2g = the policy, 2g + 1 = the opposing player
+            self.arena.set_solver_rules(refute=[rules[0][0], rules[1][0]] * n_games,
+                                        proved=[rules[0][1], rules[1][1]] * n_games)
+            self.stored_bounds = True
         self.openings = None
         if openings:
             self.openings = validate_openings(game, openings)
@@ -588,7 +599,8 @@ class LanedEngine:
     def __init__(self, game, network, n_games=4096, lanes=2, seed=0, subsequence0=None, device=None, pack=True,
                  stagger=False, cross_dedup=None, lane_sizes=None, **kw):
         # openings= / opening_period= (SelfPlayEngine): every lane gets the same book and assigns it by its
-        # lane-local game ids; proof_play= / opponent_proof_play= / proof_stop_every= / stored_bounds= reach every
+        # lane-local game ids; proof_play= / opponent_proof_play= / proof_stop_every= / stored_bounds= /
+        # solver_search= / opponent_solver_search= reach every
         # lane too (a lane's proof_stop is queued on its own stream, after the expand of the step)
         if lanes < 1 or n_games < lanes:
             raise ValueError(f"need 1 <= lanes <= n_games (lanes={lanes}, n_games={n_games})")
@@ -925,7 +937,9 @@ class LeagueEngine:
                  stored_bounds=False):
         """stored_bounds: the arena keeps the score bounds in the nodes (Arena.set_stored_bounds; for the whole
         arena, since every tree's expansions maintain them): the same games, the proof_play players' verdicts and
-        proof_stop read the root's block.  A player dict's "proof_play": True switches proof-guided play on for that player's trees (Arena.
+        proof_stop read the root's block.  A player dict's "solver_search": True | "refute" | "proved" lets that
+        player's selects read the stored bounds (Arena.set_solver_rules, per tree; stored bounds come with it; a
+        hard-coded player ignores it).  A player dict's "proof_play": True switches proof-guided play on for that player's trees (Arena.
         set_proof_play; per player, so one net can meet itself with and without it; a hard-coded player ignores it).
         proof_stop_every=N > 0: after every N-th simulation step of a ply a searching tree with proof play whose root
         is solved starts no more sims (Arena.proof_stop); needs a proof_play player and search_threads > 1.
@@ -1013,6 +1027,12 @@ class LeagueEngine:
         self.stored_bounds = bool(stored_bounds)
         if self.stored_bounds:  # (no game has started)
             a.set_stored_bounds()
+        # a player dict's "solver_search": True | "refute" | "proved" -> the rule bits of that player's trees
+        rules = [solver_search_rules(x) for x in per_tree("solver_search", False)]
+        self.solver_search = any(any(r) for r in rules)
+        if self.solver_search:
+            a.set_solver_rules(refute=[r[0] for r in rules], proved=[r[1] for r in rules])
+            self.stored_bounds = True
         self.record_games = bool(record_games)
         self._records = None
         if self.record_games:

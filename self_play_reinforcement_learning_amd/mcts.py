@@ -20,7 +20,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from .arena import GAMES, Arena, game_of_env
+from .arena import GAMES, Arena, game_of_env, solver_search_rules
 from .base_model import Policy
 from .evaluator import make_evaluator
 
@@ -73,9 +73,10 @@ class MCTreeSearch(Policy):
                  batch_size=64, memory_size=200000, min_memory=20000, update_nn=True, starting_state_dict=None,
                  thread_count=4, strong_play=False, q_average=True, alpha=1, env_gen=None, evaluator=None,
                  seed=None, device=None, rng="philox", cpuct=4, x_noise=0.25, threading=False, proof_play=False,
-                 stored_bounds=False):
+                 stored_bounds=False, solver_search=False):
         network = network if network is not None else evaluator
         env = env if env is not None else env_gen
+        rules = solver_search_rules(solver_search)  # (a bad option raises before anything is built)
         if network is None or env is None:
             raise TypeError("MCTreeSearch needs `network` and `env` (or the legacy `evaluator` / `env_gen`)")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -120,6 +121,12 @@ class MCTreeSearch(Policy):
         self.stored_bounds = bool(stored_bounds)
         if self.stored_bounds:
             self._arena.set_stored_bounds()
+        # solver_search=True | "refute" | "proved": the selects read the stored bounds (Arena.set_solver_rules; it
+        # switches stored bounds on): a refuted child draws no sims, a sim that reaches a solved child ends there
+        self.solver_search = solver_search
+        if any(rules):
+            self._arena.set_solver_rules(*rules)
+            self.stored_bounds = True
         self.temp_memory = []
         self.moves_played = 0
         # weights changed (update_from_memory / load_state_dict): the evaluator's folded / packed copy is
@@ -331,7 +338,7 @@ class MCTreeSearch(Policy):
 @torch.no_grad()
 def analyse_positions(game, network, positions, iterations, search_threads=1, x_noise=0.25, seed=0, alpha=1.0,
                       strong_play=False, cpuct=4.0, player=1, device=None, dtype=torch.float16, rng="philox",
-                      pv_len=0, tree=None, bounds=False, stored_bounds=False):
+                      pv_len=0, tree=None, bounds=False, stored_bounds=False, solver_search=False):
     """The search's answer for a batch of positions, each a move sequence from the empty board.
 
     One tree-mode arena of one tree per position: reset(player), one play_action step per ply (a tree whose
@@ -351,11 +358,14 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
     move_lo, move_hi int8 [n, A], bound_best int8 [n], bound_nodes int32 [n], and keep int32 [n], the moves
     proof-guided play would choose among (Arena.proof_moves_batch; bit a: move a).  None of them changes the other
     keys.  stored_bounds=True keeps the score bounds in the nodes (Arena.set_stored_bounds): the same outputs, `keep`
-    read from the root's stored block, and tree=dict(..., bounds=True) lists the stored entries."""
+    read from the root's stored block, and tree=dict(..., bounds=True) lists the stored entries.
+    solver_search=True | "refute" | "proved" searches with the stored bounds (Arena.set_solver_rules; stored bounds
+    come with it): other visit counts, still sound bounds; out["solver_stats"] then holds Arena.solver_stats()."""
     from .openings import validate_openings
 
     game = game if isinstance(game, str) else game_of_env(game)
     seqs = validate_openings(game, positions)
+    rules = solver_search_rules(solver_search)  # (a bad option raises before anything is built)
     n = len(seqs)
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     if isinstance(network, torch.nn.Module):
@@ -367,6 +377,8 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
     try:
         if stored_bounds:
             arena.set_stored_bounds()
+        if any(rules):
+            arena.set_solver_rules(*rules)
 
         def eval_expand(count):
             if count:
@@ -397,6 +409,8 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
             b = arena.bounds_batch(trees)
             out.update(bound_lo=b["lo"], bound_hi=b["hi"], move_lo=b["move_lo"], move_hi=b["move_hi"],
                        bound_best=b["best"], bound_nodes=b["nodes"], keep=arena.proof_moves_batch(trees)["keep"])
+        if any(rules):
+            out["solver_stats"] = arena.solver_stats()
         arena.check()
     finally:
         arena.close()

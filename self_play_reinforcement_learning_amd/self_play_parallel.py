@@ -194,7 +194,8 @@ class SelfPlayScheduler:
         threads = self._resolve_threads(inference_proxy)
         ekw = dict(iterations=kw.get("iterations", 100), alpha=kw.get("alpha", 1),
                    strong_play=kw.get("strong_play", False), seed=self.seed + 7919 * self.rank, device=self.device,
-                   search_threads=max(1, threads), proof_play=bool(kw.get("proof_play", False)))
+                   search_threads=max(1, threads), proof_play=bool(kw.get("proof_play", False)),
+                   stored_bounds=bool(kw.get("stored_bounds", False)), solver_search=kw.get("solver_search", False))
         lanes = self.lanes if self.lanes is not None else (2 if n_games >= 1024 else 1)
         if lanes > 1 and n_games >= 2 * lanes:
             self.engine = LanedEngine(self.game, self.network, n_games=n_games, lanes=lanes, **ekw)
@@ -434,7 +435,11 @@ class SelfPlayScheduler:
                               seed=self.seed + 104729 + 7919 * self.rank, device=self.device, opponent=opponent,
                               record=False, search_threads=self._search_threads, openings=openings,
                               proof_play=bool(kw.get("proof_play", False)),
-                              opponent_proof_play=bool(okw.get("proof_play", False)), **opp_kw), per_rank
+                              opponent_proof_play=bool(okw.get("proof_play", False)),
+                              # (the bounds are kept for the whole arena: either side's stored_bounds switches them on)
+                              stored_bounds=bool(kw.get("stored_bounds", False) or okw.get("stored_bounds", False)),
+                              solver_search=kw.get("solver_search", False),
+                              opponent_solver_search=okw.get("solver_search", False), **opp_kw), per_rank
 
     def _play_evaluation(self, n_games, openings=None, records=None):
         """n_games evaluation games over all ranks (task i -> swap_sides = i odd, update=False);

@@ -80,6 +80,26 @@ def proof_move_set(lo, hi, move_lo, move_hi):
     return int(mask[0]) if scalar else mask
 
 
+def solver_select(move_lo, move_hi, expanded=None):
+    """The two rules of solver-aware search (include/spmcts.h spmcts_set_solver_rules; csrc/arena_solver.h
+    sb_refuted / sb_proved) on the stored entries of one node's child block, move_lo / move_hi [A] or [n, A] with
+    -128 for an illegal move: (refuted, proved, sign), numpy arrays of the input's shape.  refuted[a]: move a is
+    legal and move_hi[a] < lo, lo the largest move_lo of the block -- it cannot reach what a sibling already
+    secures; the move that secures lo is never refuted.  proved[a]: move a is legal and move_lo[a] == move_hi[a],
+    its score is known; `expanded` (bools of the same shape, optional) restricts it to the children that have a
+    block, as the search does (a move that ends the game is solved too, but it keeps the terminal path).  sign[a]:
+    the sign of that score for the player to move, 0 where not proved."""
+    arr = lambda x: np.asarray(x.cpu() if hasattr(x, "cpu") else x).astype(np.int64)  # noqa: E731
+    mlo, mhi = arr(move_lo), arr(move_hi)
+    legal = mlo != BOUND_ILLEGAL
+    lo = np.where(legal, mlo, BOUND_ILLEGAL).max(axis=-1, keepdims=True)
+    refuted = legal & (mhi < lo)
+    proved = legal & (mlo == mhi)
+    if expanded is not None:
+        proved &= np.asarray(expanded, dtype=bool)
+    return refuted, proved, np.where(proved, np.sign(mlo), 0)
+
+
 def describe_proof_moves(keep):
     """The kept moves of a mask as text: "keeps 2 3" (proof_move_set's mask; Arena.proof_moves_batch's keep)."""
     return "keeps " + " ".join(str(a) for a in range(32) if (int(keep) >> a) & 1)
