@@ -419,6 +419,26 @@ int spmcts_tree_export_bounds_batch(spmcts_arena *h, const int32_t *trees_dev, i
                                     int8_t *move_lo_dev, int8_t *move_hi_dev, void *work_dev, uint64_t work_bytes,
                                     spmcts_stream stream);
 
+/* ---- mirror symmetry ---------------------------------------------------------- */
+/* Every board here is left-right symmetric.  M maps cell (x, y) to (W-1-x, y); the action map m is a -> W-1-a on the
+ * gravity boards and a = x*H + y -> (W-1-x)*H + y on tictactoe.  With SPMCTS_SYM_MIRROR a leaf's network input
+ * (own, opp) is put in canonical form before it is keyed and encoded: it is replaced by (M own, M opp) iff that pair
+ * is smaller, as two unsigned 64-bit masks of the board.h layout, own first (a self-symmetric position is never
+ * flipped).  Leaf rows, outputs, peer rows and cache records are canonical; a flipped leaf's expansion reads prior a
+ * from prob m(a) of its row, so node priors, the sim cap's stash, Move records and every read-out stay in the tree's
+ * orientation.  The search then runs the function f(x) = g(x) where x is not flipped, else m(g(Mx).p), g(Mx).v: a
+ * position and its mirror image share one row, and f(Mx) = m(f(x)) bit for bit.  Mode 0 (the default) launches the
+ * kernels of an arena without the feature.
+ * -2: after the arena's first search or game start, or on an arena paired by spmcts_set_leaf_peer (which refuses
+ * lanes of different modes, -3); -3: unknown mode. */
+enum { SPMCTS_SYM_NONE = 0, SPMCTS_SYM_MIRROR = 1 };
+int spmcts_set_symmetry(spmcts_arena *h, int32_t mode);
+int spmcts_get_symmetry(const spmcts_arena *h);
+/* The host twin of the rule (no GPU): board int8 [W][H] and the player to move -> canon int8 [W][H] with own = +1,
+ * opp = -1 in canonical orientation, *flipped = 1 iff the mirror image was taken. */
+int spmcts_canonical_host(int32_t game, int32_t width, int32_t height, const int8_t *board /*[W][H]*/, int32_t player,
+                          int8_t *canon /*[W][H], own = +1*/, int32_t *flipped);
+
 /* ---- games-level API (SelfPlayer.play_episode state machine) -------------- */
 /* Start games in the listed slots (selfplayworker.py:172-179): both trees reset,
  * swap_sides = game id odd (self_play_parallel.py:237).  Game ids continue from

@@ -25,7 +25,10 @@ proof_moves_batch, proof_last, proof_stats, proof_stop; tree.proof_move_set, the
 the bounds in the nodes (stored_bounds= of MCTreeSearch / SelfPlayEngine: Arena.set_stored_bounds,
 Arena.export_subtrees(bounds=True), TreeView.node_bounds), and searching with them (solver_search= of MCTreeSearch /
 SelfPlayEngine / LanedEngine / a LeagueEngine player / analyse_positions: Arena.set_solver_rules, solver_stats;
-tree.solver_select, the two rules' host form).
+tree.solver_select, the two rules' host form), and the boards' mirror symmetry (symmetry.py: mirror_boards,
+mirror_actions, mirror_probs, mirror_moves, canonical, library_canonical, SymmetricNet; symmetry="mirror" of
+MCTreeSearch / the engines / analyse_positions: Arena.set_symmetry; DeviceReplay.sample_batch(mirror=True),
+deduplicate(symmetric=True)).
 """
 from .base_model import BasePlayer, ModelContainer, Policy, TrainableModel  # noqa: F401
 from .memory import Memory  # noqa: F401
@@ -59,6 +62,13 @@ _LAZY = {
     "solver_select": ".tree",
     "enumerate_openings": ".openings",
     "validate_openings": ".openings",
+    "mirror_boards": ".symmetry",
+    "mirror_actions": ".symmetry",
+    "mirror_probs": ".symmetry",
+    "mirror_moves": ".symmetry",
+    "canonical": ".symmetry",
+    "library_canonical": ".symmetry",
+    "SymmetricNet": ".symmetry",
     "SelfPlayScheduler": ".self_play_parallel",
     "Connect4Env": ".envs",
     "TicTacToeEnv": ".envs",

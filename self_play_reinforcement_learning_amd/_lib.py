@@ -20,6 +20,7 @@ LEAF_F32, LEAF_F16, LEAF_BF16, LEAF_BOARD_I64 = 0, 1, 2, 3
 WLAYOUT_32X32, WLAYOUT_M16 = 0, 1  # spmcts_tower_weight_layout (include/spmcts.h SPMCTS_WLAYOUT_*)
 NCHW, NHWC = 0, 1
 PLAYER_MCTS, PLAYER_RANDOM, PLAYER_LOOKAHEAD, PLAYER_NEGAMAX = 0, 1, 2, 3
+SYM_NONE, SYM_MIRROR = 0, 1  # spmcts_set_symmetry (include/spmcts.h SPMCTS_SYM_*)
 
 ERR_FLAGS = {
     0x1: "node pool exhausted",
@@ -142,6 +143,9 @@ _SIGS = {
     "spmcts_search_progress": [_P, _P, _P, _P],
     "spmcts_tree_export_bounds_batch": [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                         _P, _U64, _P],
+    "spmcts_set_symmetry": [_P, _I32],
+    "spmcts_get_symmetry": [_P],
+    "spmcts_canonical_host": [_I32, _I32, _I32, _P, _I32, _P, ctypes.POINTER(_I32)],
     "spmcts_set_league": [_P, _P, _I32],
     "spmcts_league_segments": [_P, _P],
     "spmcts_league_route": [_P, _P, _P, _I32, _P, _P, _P],

@@ -222,6 +222,21 @@ class Arena:
         call("spmcts_set_leaf_dedup", self.h, int(bool(on)))
         self.leaf_dedup = bool(on) and self.search_threads > 1
 
+    symmetry = None
+
+    def set_symmetry(self, mode):
+        """Mirror symmetry (include/spmcts.h spmcts_set_symmetry): "mirror" puts every leaf's network input in
+        canonical form (symmetry.canonical), so a position and its mirror image share one row, one peer row and
+        one cache record, and the search runs symmetry.SymmetricNet of the network.  None: off (the default).
+        Before the arena's first search or game start and before set_leaf_peer; SpmctsError (-2) afterwards."""
+        call("spmcts_set_symmetry", self.h, symmetry_mode(mode))
+        self.symmetry = "mirror" if symmetry_mode(mode) else None
+
+    def leaf_rows(self):
+        """The pending leaves gathered into network rows, as the network's input tensor (sync on the count)."""
+        self.leaf_rows_async()
+        return self.leaves(self._read_count())
+
     def set_leaf_peer(self, leader):
         """Cross-lane leaf dedup (include/spmcts.h spmcts_set_leaf_peer): in each simulation step a pending leaf
         whose network input `leader` (another lane's arena, stepped first) evaluates in the same step takes the
@@ -890,6 +905,18 @@ def solver_search_rules(option):
     if option in ("refute", "proved"):
         return option == "refute", option == "proved"
     raise ValueError(f'solver_search must be True, False, "refute" or "proved", got {option!r}')
+
+
+def symmetry_mode(option):
+    """The symmetry= option of the arena, players and engines as the library's mode: None / False -> 0 (off),
+    "mirror" -> SPMCTS_SYM_MIRROR.  An integer passes through (the library refuses an unknown one)."""
+    if option is None or option is False:
+        return _lib.SYM_NONE
+    if option == "mirror":
+        return _lib.SYM_MIRROR
+    if isinstance(option, (int, np.integer)) and not isinstance(option, bool):
+        return int(option)
+    raise ValueError(f'symmetry must be None or "mirror", got {option!r}')
 
 
 def table_net_eval(game, leaves, leaf_format, leaf_layout, salt=0, salts=None):

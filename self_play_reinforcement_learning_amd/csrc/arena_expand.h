@@ -4,7 +4,9 @@
 // kernel: expand + backup of network-evaluated leaves (mcts.py:316-321, :94-98)
 // ----------------------------------------------------------------------------
 // SB (arena_solver.h): the new block is stamped with its moves' score bounds and the change carried up the path.
-template <class G, bool SB = false>
+// SYM (spmcts_set_symmetry): rows are in canonical orientation (arena_rows.h, leaf_key); a leaf whose input was
+// flipped takes prior a from prow[m(a)], so node priors are in the tree's orientation.
+template <class G, bool SB = false, bool SYM = false>
 __global__ __launch_bounds__(64) void k_expand(View v, const float *probs0, const float *values0,
                                                const float *probs1, const float *values1) {
   constexpr int P = G::APAD;
@@ -29,7 +31,13 @@ __global__ __launch_bounds__(64) void k_expand(View v, const float *probs0, cons
     const size_t ci = nb + (size_t)blk * P + lane;
     nd_n<P>(v, ci) = 0;
     nd_w<P>(v, ci) = 0.0;
-    nd_p<P>(v, ci) = lane < G::A ? prow[lane] : 0.f;
+    int src = lane;
+    if constexpr (SYM) {
+      const bool pm = v.lmover[tree] > 0;  // (K = 1: the tree is its pending slot)
+      uint64_t own = pm ? v.lpos[tree] : v.lneg[tree], opp = pm ? v.lneg[tree] : v.lpos[tree];
+      if (canonical_pair<G>(own, opp) && lane < G::A) src = mirror_action<G>(lane);
+    }
+    nd_p<P>(v, ci) = lane < G::A ? prow[src] : 0.f;
     nd_c<P>(v, ci) = -1;
     nd_f<P>(v, ci) = 0;
   }
@@ -88,7 +96,10 @@ constexpr int EXPAND_THREADS = 256;
 // short dependent LDS / permute / FP64 latencies, not memory round trips): DESIGN.md §4.
 constexpr int SELECT_THREADS = 64;
 
-template <class G, int THREADS, bool ROWS, bool SB = false>
+// SYM (spmcts_set_symmetry; only with ROWS): lane j < K works out whether its slot's input was flipped, from the
+// record it holds anyway, and the row read below takes prob m(lane) of a flipped slot's canonical row.  The LDS
+// copy, the node priors and the stash are then in the tree's orientation, as without the mode.
+template <class G, int THREADS, bool ROWS, bool SB = false, bool SYM = false>
 __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, const float *values0,
                                                const float *probs1, const float *values1) {
   constexpr int P = G::APAD;
@@ -148,15 +159,22 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
   // the network outputs of the pending slots (second round trip: they depend on the rows)
   {
     float pr[KMAX], vr[KMAX];
+    int my_flip = 0, mlane = lane;
+    if constexpr (ROWS && SYM) {
+      uint64_t own = my_mover > 0 ? my_pos : my_neg, opp = my_mover > 0 ? my_neg : my_pos;
+      my_flip = canonical_pair<G>(own, opp) ? 1 : 0;
+      if (lane < G::A) mlane = mirror_action<G>(lane);
+    }
 #pragma unroll
     for (int j = 0; j < KMAX; ++j) {
       const int nj = __shfl(my_need, gbase + j, 64), row = __shfl(my_srow, gbase + j, 64);
+      const int fj = (ROWS && SYM) ? __shfl(my_flip, gbase + j, 64) : 0;
       pr[j] = 0.f;
       vr[j] = 0.f;
       if (ROWS && j < K && nj == NEED_ROW) {
         const bool s1 = row >= v.seg1;
         const float *prow = s1 ? probs1 + (size_t)(row - v.seg1) * G::A : probs0 + (size_t)row * G::A;
-        if (lane < G::A) pr[j] = prow[lane];
+        if (lane < G::A) pr[j] = prow[fj ? mlane : lane];
         vr[j] = s1 ? values1[row - v.seg1] : values0[row];
       } else if (j < K && nj == NEED_STASH) {  // evaluated in an earlier step, kept across a pause
         const size_t sj = (size_t)tree * K + j;
@@ -358,10 +376,10 @@ __device__ __forceinline__ void expand_vl_body(View v, const float *probs0, cons
   }
 }
 
-template <class G, bool SB = false>
+template <class G, bool SB = false, bool SYM = false>
 __global__ __launch_bounds__(EXPAND_THREADS) void k_expand_vl(View v, const float *probs0, const float *values0,
                                                   const float *probs1, const float *values1) {
-  expand_vl_body<G, EXPAND_THREADS, true, SB>(v, probs0, values0, probs1, values1);
+  expand_vl_body<G, EXPAND_THREADS, true, SB, SYM>(v, probs0, values0, probs1, values1);
 }
 
 // (its domain: the active list, View::dn = its length, dpack = 1: spmcts_select_tree)

@@ -13,11 +13,17 @@
 // receives exactly the outputs its own row would have produced.  Owner of a key = its lowest slot
 // (deterministic); the table is cleared by generation stamps instead of a memset per step.
 // ----------------------------------------------------------------------------
-template <class G>
+// SYM (spmcts_set_symmetry): the key is the canonical pair (board.h, canonical_pair), so a position and its mirror
+// image share a row, a peer row and a cache record; every kernel that takes a key is instantiated for both modes,
+// and the SYM = false ones are the kernels of an arena without the mode (View has no field for it).
+// k_dedup_insert recomputes the key of the slot it collides with on every probe: with SYM that is the mirror's
+// register arithmetic behind the three loads the key already costs, and no per-slot state to keep current.
+template <class G, bool SYM = false>
 __device__ __forceinline__ void leaf_key(const View &v, int t, uint64_t &own, uint64_t &opp) {
   const int mover = v.lmover[t];
   own = mover > 0 ? v.lpos[t] : v.lneg[t];
   opp = mover > 0 ? v.lneg[t] : v.lpos[t];
+  if constexpr (SYM) canonical_pair<G>(own, opp);
   if (v.tnet[t / v.K]) own |= 1ull << 63;  // rows of the two networks never merge (cell bits < 63)
 }
 
@@ -31,14 +37,14 @@ __device__ __forceinline__ uint32_t leaf_hash(uint64_t a, uint64_t b) {
   return (uint32_t)x;
 }
 
-template <class G>
+template <class G, bool SYM = false>
 __global__ __launch_bounds__(256) void k_dedup_insert(View v) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= v.dn * v.K) return;
   const int t = dom_slot(v, c);
   if (t < 0 || v.need[t] != NEED_ROW) return;  // (a NEED_STASH slot is evaluated already: no row, here and below)
   uint64_t own, opp;
-  leaf_key<G>(v, t, own, opp);
+  leaf_key<G, SYM>(v, t, own, opp);
   const unsigned long long mine = ((unsigned long long)v.dgen << 32) | (uint32_t)t;
   unsigned long long *tab = (unsigned long long *)v.dtab;
   uint32_t h = leaf_hash(own, opp) & (uint32_t)v.dmask;
@@ -55,7 +61,7 @@ __global__ __launch_bounds__(256) void k_dedup_insert(View v) {
       w = old;
     }
     uint64_t so, sp;
-    leaf_key<G>(v, (int)(uint32_t)w, so, sp);
+    leaf_key<G, SYM>(v, (int)(uint32_t)w, so, sp);
     if (so == own && sp == opp) {
       atomicMin(tab + h, mine);  // the lowest slot of the key owns the row
       v.dent[t] = (int)h;
@@ -130,10 +136,10 @@ __device__ __forceinline__ int cache_find(const View &v, uint64_t own, uint64_t 
 }
 
 // an owner slot's key in the cache: down 3, the entry in xc, its generation renewed (kept while in use)
-template <class G>
+template <class G, bool SYM = false>
 __device__ __forceinline__ bool cache_hit(const View &v, int t) {
   uint64_t own, opp;
-  leaf_key<G>(v, t, own, opp);
+  leaf_key<G, SYM>(v, t, own, opp);
   const int e = cache_find(v, own, opp);
   if (e < 0) return false;
   __hip_atomic_store(cache_rec(v, e), ((unsigned long long)v.cgen << 32) | CACHE_READY, __ATOMIC_RELAXED,
@@ -142,7 +148,7 @@ __device__ __forceinline__ bool cache_hit(const View &v, int t) {
   return true;
 }
 
-template <class G>
+template <class G, bool SYM = false>
 __global__ __launch_bounds__(256) void k_dedup_owner(View v) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= v.dn * v.K) return;
@@ -152,11 +158,11 @@ __global__ __launch_bounds__(256) void k_dedup_owner(View v) {
     d = v.need[t] == NEED_ROW;  // no dedup: every leaf that waits for the network owns its row
   } else if (t >= 0) {
     const bool own = v.need[t] == NEED_ROW && (int)(uint32_t)v.dtab[v.dent[t]] == t;
-    d = own ? (v.cwin && cache_hit<G>(v, t) ? 3 : 1) : 0;
+    d = own ? (v.cwin && cache_hit<G, SYM>(v, t) ? 3 : 1) : 0;
     v.down[t] = (uint8_t)d;
     if (own && v.lead) {
       uint64_t a, b;
-      leaf_key<G>(v, t, a, b);
+      leaf_key<G, SYM>(v, t, a, b);
       v.okey[2 * (size_t)t] = a;
       v.okey[2 * (size_t)t + 1] = b;
     }
@@ -170,7 +176,7 @@ __global__ __launch_bounds__(256) void k_dedup_owner(View v) {
 // older one).  A hit takes the leader's row: down 2, xpeer = the leader's owner slot.  Outputs are pure
 // functions of the leaf planes (the fused trunk is batch-independent), so the leaf still gets exactly
 // the outputs its own row would have produced.
-template <class G>
+template <class G, bool SYM = false>
 __global__ __launch_bounds__(256) void k_dedup_owner_peer(View v, const uint64_t *ptab, const uint64_t *pkey,
                                                           const uint8_t *pdown, int pmask, uint32_t pgen) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -183,14 +189,14 @@ __global__ __launch_bounds__(256) void k_dedup_owner_peer(View v, const uint64_t
   int d = 0, xp = -1;
   if (v.need[t] == NEED_ROW && (int)(uint32_t)v.dtab[v.dent[t]] == t) {
     d = 1;
-    if (v.cwin && cache_hit<G>(v, t)) {  // the follower's own cache first: no wait on the leader's outputs
+    if (v.cwin && cache_hit<G, SYM>(v, t)) {  // the follower's own cache first: no wait on the leader's outputs
       v.down[t] = 3;
       v.xpeer[t] = -1;
       v.crow[c] = t * 4 + 3;
       return;
     }
     uint64_t own, opp;
-    leaf_key<G>(v, t, own, opp);
+    leaf_key<G, SYM>(v, t, own, opp);
     uint32_t h = leaf_hash(own, opp) & (uint32_t)pmask;
     for (int probe = 0; probe <= pmask; ++probe) {
       const unsigned long long w = ptab[h];
@@ -229,7 +235,7 @@ __global__ __launch_bounds__(256) void k_peer_push(View v, const int32_t *psrow,
 // its own network's, down 2: the leader's, pushed before this -- unless the table is the leader's own, which
 // the leader fills) puts them in the cache under the current generation (nothing is cached when no entry
 // within CACHE_PROBES is free).  Duplicates (down 0) read their owner's row.
-template <class G>
+template <class G, bool SYM = false>
 __global__ __launch_bounds__(256) void k_cache_io(View v, float *probs0, float *values0, float *probs1,
                                                   float *values1) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -253,7 +259,7 @@ __global__ __launch_bounds__(256) void k_cache_io(View v, float *probs0, float *
   }
   if (d == 2 && v.cshared) return;
   uint64_t own, opp;
-  leaf_key<G>(v, t, own, opp);
+  leaf_key<G, SYM>(v, t, own, opp);
   uint32_t h = leaf_hash(own, opp) & (uint32_t)v.cmask;
   const unsigned long long gen = (unsigned long long)v.cgen << 32;
   for (int p = 0; p < CACHE_PROBES; ++p) {
@@ -422,7 +428,7 @@ __device__ __forceinline__ bool row_live(const View &v, int row) {
 // ----------------------------------------------------------------------------
 // kernel: leaf encoding (preprocess, games/general/modules.py:115-125; input = state*mover)
 // ----------------------------------------------------------------------------
-template <class G>
+template <class G, bool SYM = false>
 __global__ void k_encode(View v, void *out) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int cell = (int)(gid % G::CELLS);
@@ -435,8 +441,9 @@ __global__ void k_encode(View v, void *out) {
   const int x = cell / G::H, y = cell % G::H;
   const uint64_t bit = 1ull << cell_bit<G>(x, y);
   const int mover = v.lmover[t];
-  const uint64_t own = mover > 0 ? v.lpos[t] : v.lneg[t];
-  const uint64_t opp = mover > 0 ? v.lneg[t] : v.lpos[t];
+  uint64_t own = mover > 0 ? v.lpos[t] : v.lneg[t];
+  uint64_t opp = mover > 0 ? v.lneg[t] : v.lpos[t];
+  if constexpr (SYM) canonical_pair<G>(own, opp);  // the row in canonical orientation: cell (x, y) of the mirror image
   const int c_own = (own & bit) ? 1 : 0, c_opp = (opp & bit) ? 1 : 0;
   const int c_emp = 1 - c_own - c_opp;
   if (v.leaf_format == SPMCTS_LEAF_BOARD_I64) {

@@ -185,6 +185,41 @@ SPM_HD int8_t cell_value(Board b, int x, int y) {
   return (b.pos & bit) ? int8_t(1) : ((b.neg & bit) ? int8_t(-1) : int8_t(0));
 }
 
+// ---- left-right mirror symmetry ----------------------------------------------
+// M maps cell (x, y) to (W - 1 - x, y): column x's CB bits (its sentinel with them, zero) move to column
+// W - 1 - x.  8x7 has CB = 8, a byte per column: M is a byte swap.  Otherwise one delta swap per column pair.
+template <class G>
+SPM_HD uint64_t mirror_mask(uint64_t m) {
+  if (G::W == 8 && G::CB == 8) return __builtin_bswap64(m);
+#pragma unroll
+  for (int x = 0; x < G::W / 2; ++x) {
+    const int d = (G::W - 1 - 2 * x) * G::CB;
+    const uint64_t t = ((m >> d) ^ m) & (((1ull << G::CB) - 1ull) << (x * G::CB));
+    m ^= t | (t << d);
+  }
+  return m;
+}
+
+// the action map m of M (an involution): the mirrored column, or the mirrored cell of a = x * H + y
+template <class G>
+SPM_HD int mirror_action(int a) {
+  return G::GRAVITY ? G::W - 1 - a : (G::W - 1 - a / G::H) * G::H + a % G::H;
+}
+
+// The canonical form of a network input (own, opp): the mirror image iff (M own, M opp) < (own, opp) as pairs
+// of unsigned integers, own first; a self-symmetric position is never flipped.  Returns whether it flipped.
+// The one statement of the rule: leaf keys, k_encode, the expands' row reads and spmcts_canonical_host use it.
+template <class G>
+SPM_HD bool canonical_pair(uint64_t &own, uint64_t &opp) {
+  const uint64_t mo = mirror_mask<G>(own), mp = mirror_mask<G>(opp);
+  const bool flip = mo < own || (mo == own && mp < opp);
+  if (flip) {
+    own = mo;
+    opp = mp;
+  }
+  return flip;
+}
+
 // ---- deterministic table network (oracle/table_net.py) ----------------------
 SPM_HD uint64_t splitmix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;

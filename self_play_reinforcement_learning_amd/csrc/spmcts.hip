@@ -158,6 +158,10 @@ struct spmcts_arena {
   bool sb = false;
   // solver-aware search (spmcts_set_solver_rules): the rule bits' and the statistics' allocations (View::sv_*)
   std::vector<void *> solver_allocs;
+  // mirror symmetry (spmcts_set_symmetry): the arena launches the SYM = true kernels (LAUNCH_SYM, LAUNCH_SB_SYM
+  // below); `begun`: a search or a game has started, after which the mode is fixed
+  int sym = 0;
+  bool begun = false;
 };
 
 static bool league_on(const spmcts_arena *h) { return h->lg.n > 0; }
@@ -390,6 +394,20 @@ static int launch(void (*k)(P...), long long n, int B, hipStream_t s, const A &.
     return (h)->sb ? launch(k<decltype(game_), true>, n, B, s, __VA_ARGS__)                                 \
                    : launch(k<decltype(game_), false>, n, B, s, __VA_ARGS__);                               \
   })
+// the same for the kernels that take a leaf key or read a row (template <class G, bool SYM> and
+// <class G, bool SB, bool SYM>): the canonical-form instantiation once the arena's symmetry mode is on
+#define LAUNCH_SYM(h, k, n, B, s, ...)                                                                      \
+  with_game((h)->cfg.game, (h)->W, (h)->H, [&](auto game_) {                                                \
+    return (h)->sym ? launch(k<decltype(game_), true>, n, B, s, __VA_ARGS__)                                \
+                    : launch(k<decltype(game_), false>, n, B, s, __VA_ARGS__);                              \
+  })
+#define LAUNCH_SB_SYM(h, k, n, B, s, ...)                                                                   \
+  with_game((h)->cfg.game, (h)->W, (h)->H, [&](auto game_) {                                                \
+    using G_ = decltype(game_);                                                                             \
+    if ((h)->sym)                                                                                           \
+      return (h)->sb ? launch(k<G_, true, true>, n, B, s, __VA_ARGS__) : launch(k<G_, false, true>, n, B, s, __VA_ARGS__); \
+    return (h)->sb ? launch(k<G_, true, false>, n, B, s, __VA_ARGS__) : launch(k<G_, false, false>, n, B, s, __VA_ARGS__); \
+  })
 
 // ---- negamax launches --------------------------------------------------------
 // A launch's worst-case node bound, positions * sum_{k = 1 .. D} A^k, stays below NM_LAUNCH_NODES: a batch (and
@@ -548,6 +566,7 @@ int spmcts_set_leaf_peer(spmcts_arena *h, spmcts_arena *leader) {
     return fail(-3, "leader and follower must play the same game on the same device");
   if (h->v.K < 2 || leader->v.K != h->v.K) return fail(-3, "cross-lane dedup needs equal search_threads > 1");
   if (h->v.seg1 < h->v.NS || leader->v.seg1 < leader->v.NS) return fail(-3, "cross-lane dedup: single-network arenas");
+  if (leader->sym != h->sym) return fail(-3, "leader and follower must run the same symmetry mode (spmcts_set_symmetry)");
   for (hipEvent_t *e : {&leader->ev_ins, &h->ev_rows, &h->ev_push, &h->ev_lead})
     if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
   leader->followers.push_back(h);
@@ -617,6 +636,7 @@ int spmcts_search_begin(spmcts_arena *h, const int32_t *trees_dev, int32_t n, sp
   if (!h) return fail(-1, "null arena");
   if (n > std::max(h->v.T, h->v.G)) return fail(-3, "too many active trees");
   h->n_active = n;
+  h->begun = true;
   h->games_list = false;  // a caller's list: any order, so its steps launch at full width (launch_rows)
   h->v.sim = 0;
   if (h->v.cwin) ++h->v.cgen;  // a new evaluation-cache generation per search
@@ -659,6 +679,7 @@ static bool peer_live(const spmcts_arena *h) { return h->peer && h->v.dedup && h
 // full-width passes rewrite down for every slot.
 static int launch_rows(spmcts_arena *h, void *leaves_dev, int32_t *leaf_count_dev, hipStream_t s, bool sim_step) {
   h->peer_step = false;
+  h->begun = true;
   h->route_step = false;  // new rows: the last route's map is stale
   h->packed_step = sim_step && h->games_list;
   for (spmcts_arena *f : h->followers)  // a leader rewrites its table, keys and (later) outputs only after the pushes
@@ -679,20 +700,20 @@ static int launch_rows(spmcts_arena *h, void *leaves_dev, int32_t *leaf_count_de
     if (++h->v.dgen == 0) ++h->v.dgen;  // generation 0 = the zeroed table
     v.dgen = h->v.dgen;
     v.lead = h->followers.empty() ? 0 : 1;
-    TRY(LAUNCH(h, k_dedup_insert, slots, 256, s, v));
+    TRY(LAUNCH_SYM(h, k_dedup_insert, slots, 256, s, v));
     if (sim_step && peer_live(h)) {
       // the leader's table and keys of this step are complete (its ev_ins), and stay so until this step's
       // rows are numbered (the leader's stream waits for our ev_rows before it moves on: spmcts_peer_push)
       const spmcts_arena *p = h->peer;
       HIP_TRY(hipStreamWaitEvent(s, p->ev_ins, 0));
       v.peer_on = 1;
-      TRY(LAUNCH(h, k_dedup_owner_peer, slots, 256, s, v, p->v.dtab, p->v.okey, p->v.down, p->v.dmask, p->v.dgen));
+      TRY(LAUNCH_SYM(h, k_dedup_owner_peer, slots, 256, s, v, p->v.dtab, p->v.okey, p->v.down, p->v.dmask, p->v.dgen));
     } else {
-      TRY(LAUNCH(h, k_dedup_owner, slots, 256, s, v));
+      TRY(LAUNCH_SYM(h, k_dedup_owner, slots, 256, s, v));
     }
     if (v.lead) HIP_TRY(hipEventRecord(h->ev_ins, s));
   } else {
-    TRY(LAUNCH(h, k_dedup_owner, slots, 256, s, v));  // no dedup: every pending slot's row flag (crow)
+    TRY(LAUNCH_SYM(h, k_dedup_owner, slots, 256, s, v));  // no dedup: every pending slot's row flag (crow)
   }
   TRY(launch(k_scan_need, SCAN_THREADS, SCAN_THREADS, s, v, leaf_count_dev));  // one block
   if (v.dedup) TRY(launch(k_dedup_alias, slots, 256, s, v));
@@ -700,7 +721,7 @@ static int launch_rows(spmcts_arena *h, void *leaves_dev, int32_t *leaf_count_de
     HIP_TRY(hipEventRecord(h->ev_rows, s));
     h->peer_step = true;  // spmcts_peer_push brings the leader's outputs before the expand
   }
-  if (leaves_dev) TRY(LAUNCH(h, k_encode, slots * h->cells, 256, s, v, leaves_dev));
+  if (leaves_dev) TRY(LAUNCH_SYM(h, k_encode, slots * h->cells, 256, s, v, leaves_dev));
   return 0;
 }
 
@@ -742,15 +763,15 @@ int spmcts_expand2(spmcts_arena *h, const float *probs0_dev, const float *values
     View v = dv;
     if (h->cache_shared_step) cache_view(h, v);
     if (v.crec != h->cache_tab) return fail(-4, "the evaluation cache table changed between a step's rows and its expand");
-    TRY(LAUNCH(h, k_cache_io, (long long)v.dn * v.K, 256, (hipStream_t)stream, v, (float *)probs0_dev,
+    TRY(LAUNCH_SYM(h, k_cache_io, (long long)v.dn * v.K, 256, (hipStream_t)stream, v, (float *)probs0_dev,
                (float *)values0_dev, (float *)probs1_dev, (float *)values1_dev));
     h->cache_step = false;
   }
   if (h->v.K > 1)  // one P-lane group per tree of the domain
-    return LAUNCH_SB(h, k_expand_vl, (long long)dv.dn * h->P, EXPAND_THREADS, (hipStream_t)stream, dv, probs0_dev,
+    return LAUNCH_SB_SYM(h, k_expand_vl, (long long)dv.dn * h->P, EXPAND_THREADS, (hipStream_t)stream, dv, probs0_dev,
                      values0_dev, probs1_dev, values1_dev);
   const long long lanes = (long long)h->v.T * h->P;  // one P-lane group per row
-  return LAUNCH_SB(h, k_expand, lanes, 64, (hipStream_t)stream, h->v, probs0_dev, values0_dev, probs1_dev, values1_dev);
+  return LAUNCH_SB_SYM(h, k_expand, lanes, 64, (hipStream_t)stream, h->v, probs0_dev, values0_dev, probs1_dev, values1_dev);
 }
 
 int spmcts_expand(spmcts_arena *h, const float *probs_dev, const float *values_dev, spmcts_stream stream) {
@@ -1053,6 +1074,7 @@ int spmcts_games_start(spmcts_arena *h, const int32_t *slots_dev, const float *p
   if (!h) return fail(-1, "null arena");
   if (h->v.G <= 0) return fail(-4, "arena has no game slots");
   if (n <= 0) return 0;
+  h->begun = true;
   hipStream_t s = (hipStream_t)stream;
   TRY(LAUNCH_SB(h, k_games_start, n, 128, s, h->v, slots_dev, priors_dev, n));
   return launch(k_games_bump_id, 1, 1, s, h->v, n);
@@ -1390,6 +1412,34 @@ int spmcts_proof_stop(spmcts_arena *h, spmcts_stream stream) {
   if (h->v.K <= 1) return fail(-4, "proof_stop needs search_threads > 1 (a sequential search has no sims left to skip)");
   if (!h->v.pf_keep) return fail(-4, "proof_stop needs proof play (spmcts_set_proof_play)");
   return LAUNCH_SB(h, k_proof_stop, (long long)h->v.T * h->P, TB_THREADS, (hipStream_t)stream, h->v);
+}
+
+// ---- mirror symmetry ------------------------------------------------------------
+int spmcts_set_symmetry(spmcts_arena *h, int32_t mode) {
+  if (!h) return fail(-1, "null arena");
+  if (mode != 0 && mode != SPMCTS_SYM_MIRROR) return fail(-3, "symmetry: unknown mode (0 or SPMCTS_SYM_MIRROR)");
+  if (mode == h->sym) return 0;
+  // rows, peer rows and cache records of one orientation rule only: fixed once a search has run or a lane is paired
+  if (h->begun) return fail(-2, "symmetry must be set before the arena's first search or game start");
+  if (h->peer || !h->followers.empty()) return fail(-2, "symmetry must be set before the arena is paired with a peer");
+  h->sym = mode;
+  return 0;
+}
+
+int spmcts_get_symmetry(const spmcts_arena *h) { return h ? h->sym : fail(-1, "null arena"); }
+
+int spmcts_canonical_host(int32_t game, int32_t width, int32_t height, const int8_t *board, int32_t player, int8_t *canon,
+                          int32_t *flipped) {
+  if (!board || !canon || !flipped) return fail(-1, "null argument");
+  return with_game(game, width, height, [&](auto g) {
+    using G = decltype(g);
+    const Board b = from_cells<G>(board);
+    uint64_t own = player > 0 ? b.pos : b.neg, opp = player > 0 ? b.neg : b.pos;
+    *flipped = canonical_pair<G>(own, opp) ? 1 : 0;
+    for (int x = 0; x < G::W; ++x)
+      for (int y = 0; y < G::H; ++y) canon[x * G::H + y] = cell_value<G>(Board{own, opp}, x, y);
+    return 0;
+  });
 }
 
 // ---- stored score bounds -----------------------------------------------------

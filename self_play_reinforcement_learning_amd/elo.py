@@ -320,11 +320,25 @@ class Elo:
                 out.append(dict(kind="random" if e["policy"] == "Random" else "lookahead"))
         return out
 
+    def league_symmetry(self, names, symmetry=None):
+        """The symmetry mode of one arena that the models `names` share (LeagueEngine's symmetry=): `symmetry` if
+        given ("mirror", or False for off), else the MCTreeSearch models' own policy_kwargs["symmetry"], which must
+        then agree: ValueError otherwise (the mode is the arena's, not a player's).  Hard-coded players have none."""
+        if symmetry is not None:
+            return symmetry or None
+        models = self.model_database.models()
+        modes = {models[n]["policy_kwargs"].get("symmetry") or None for n in names
+                 if models[n]["policy"] == "MCTreeSearch"}
+        if len(modes) > 1:
+            raise ValueError(f"the models of one arena disagree about symmetry ({sorted(map(str, modes))}): pass "
+                             "symmetry= to decide it for the arena")
+        return modes.pop() if modes else None
+
     def named_players(self, names):
         """players(names) with each dict's "name" set: the names a league's game records carry."""
         return [dict(p, name=n) for p, n in zip(self.players(names), names)]
 
-    def compare_models(self, *names, num_games=100, openings=None, record_games=False):
+    def compare_models(self, *names, num_games=100, openings=None, record_games=False, symmetry=None):
         """Play num_games games (rounded up to an even number) between every two of `names`, all C(n, 2)
         pairings in one league arena, and add the results to results.json under the reference's keys
         (elo.py:45-71).  Returns the new results per key.  openings: an opening book (a list of move lists, or
@@ -332,7 +346,9 @@ class Elo:
         opening k mod len(openings), once per colour; None = every game starts on the empty board.  The counts
         keep their keys and meaning either way.  record_games: also keep every game's move list (the arena's game
         log): each pairing's records are appended to games/<key>.json in the database directory, <key> the pairing's
-        results.json key; the records carry both players' names, so they need no turning round."""
+        results.json key; the records carry both players' names, so they need no turning round.  symmetry: "mirror"
+        searches every model's symmetry.SymmetricNet form (Arena.set_symmetry; False = off); None = the models' own
+        policy_kwargs["symmetry"], ValueError if they disagree."""
         from .arena import game_of_env
         from .engine import LeagueEngine
         from .openings import parse_openings
@@ -346,11 +362,12 @@ class Elo:
         pairings = list(itertools.combinations(range(len(names)), 2))
         game = game_of_env(self.model_database.env)
         players = self.named_players(names)
+        symmetry = self.league_symmetry(names, symmetry)
         eng = LeagueEngine(game, players, pairings, games_per_pairing=num_games,
                            seed=self.seed + 7919 * self.calls, search_threads=self.search_threads, dtype=self.dtype,
                            device=self.device, openings=parse_openings(openings, game), record_games=record_games,
                            # (kept for the whole arena: any model's stored_bounds switches them on)
-                           stored_bounds=any(p.get("stored_bounds") for p in players))
+                           stored_bounds=any(p.get("stored_bounds") for p in players), symmetry=symmetry)
         self.calls += 1
         try:
             breakdowns = eng.play()
@@ -395,7 +412,7 @@ class Elo:
         db.set_accuracy(out)
         return out
 
-    def observe(self, name_1, name_2, openings=None, out=print):
+    def observe(self, name_1, name_2, openings=None, out=print, symmetry=None):
         """The reference's main.py observe (ModelDatabase.observe with View): the two models play one game per
         colour in a league arena with the game log on, and each game is printed ply by ply
         (records.GameRecords.render).  Nothing is stored.  Returns the records."""
@@ -406,7 +423,8 @@ class Elo:
         game = game_of_env(self.model_database.env)
         eng = LeagueEngine(game, self.named_players([name_1, name_2]), [(0, 1)], games_per_pairing=2,
                            seed=self.seed + 7919 * self.calls, search_threads=self.search_threads, dtype=self.dtype,
-                           device=self.device, openings=parse_openings(openings, game), record_games=True)
+                           device=self.device, openings=parse_openings(openings, game), record_games=True,
+                           symmetry=self.league_symmetry([name_1, name_2], symmetry))
         self.calls += 1
         try:
             eng.play()
@@ -419,7 +437,7 @@ class Elo:
         return records
 
     def analyse(self, name, moves, pv_len=8, tree_depth=2, min_visits=2, out=None, bounds=False, kept_moves=False,
-                solver_search=None):
+                solver_search=None, symmetry=None):
         """One registered MCTreeSearch model's search of the position after `moves` (a move list from the empty
         board): mcts.analyse_positions with the model's own iterations / alpha / strong_play, its principal
         variation of at most pv_len moves and its tree to tree_depth (nodes with at least min_visits visits).
@@ -430,7 +448,8 @@ class Elo:
         kept_moves=True (with bounds) appends the moves proof-guided play would choose among to that line,
         "proved: win in 5 by 3; keeps 3" (analyse_positions' keep; tree.describe_proof_moves).  solver_search: True |
         "refute" | "proved" searches with the stored bounds (Arena.set_solver_rules) and adds a line with the rules'
-        counts; None = the model's own policy_kwargs["solver_search"]."""
+        counts; None = the model's own policy_kwargs["solver_search"].  symmetry: "mirror" | False, None = the
+        model's own policy_kwargs["symmetry"] (analyse_positions' symmetry=)."""
         from .arena import game_of_env
         from .mcts import analyse_positions
         from .tree import TreeView, describe_bounds, describe_proof_moves
@@ -446,7 +465,8 @@ class Elo:
                                 strong_play=bool(kw.get("strong_play", False)), device=self.device, dtype=self.dtype,
                                 pv_len=int(pv_len), tree=dict(max_nodes=2 + its, min_visits=int(min_visits),
                                                               max_depth=tree_depth), bounds=bool(bounds),
-                                solver_search=kw.get("solver_search", False) if solver_search is None else solver_search)
+                                solver_search=kw.get("solver_search", False) if solver_search is None else solver_search,
+                                symmetry=self.league_symmetry([name], symmetry))
         view = TreeView.from_export(res["tree"], 0)
         cn, cw, cp = (res[k][0].cpu().numpy() for k in ("child_n", "child_w", "child_p"))
         lines = [f"{name}: {its} simulations after moves {list(moves)}; root n={int(res['root_n'][0])} "
@@ -533,10 +553,14 @@ def main(argv=None):
                         help="analyse: add what the search's tree has proved about the position")
     parser.add_argument("--solver-search", action="store_true",
                         help="analyse: search with the stored score bounds (refuted children, proved sims)")
+    parser.add_argument("--symmetry", default=None, choices=["mirror", "off"],
+                        help="compare_models / analyse / observe: evaluate leaves in canonical (mirror) orientation, "
+                             "or not; default: the models' own setting")
     parser.add_argument("--kept-moves", action="store_true",
                         help="analyse --bounds: add the moves proof-guided play would choose among to that line")
     args = parser.parse_args(argv)
     env = {"connect4": Connect4Env, "tictactoe": TicTacToeEnv}[args.game](*[int(x) for x in args.board_size or []])
+    symmetry = {None: None, "mirror": "mirror", "off": False}[args.symmetry]
     elo = Elo(ModelDatabase(args.dir, env))
     if args.command == "calculate_elo":
         print(json.dumps(elo.calculate_elo(), indent=1, sort_keys=True))
@@ -545,17 +569,17 @@ def main(argv=None):
     elif args.command == "observe":
         if not args.p or len(args.p) != 2:
             parser.error("observe needs --p with two model names")
-        elo.observe(*args.p, openings=args.openings)
+        elo.observe(*args.p, openings=args.openings, symmetry=symmetry)
     elif args.command == "analyse":
         if not args.p or len(args.p) != 1:
             parser.error("analyse needs --p with one model name")
         elo.analyse(args.p[0], args.moves, pv_len=args.pv, tree_depth=args.tree_depth, min_visits=args.min_visits,
                     out=print, bounds=args.bounds, kept_moves=args.kept_moves,
-                    solver_search=True if args.solver_search else None)
+                    solver_search=True if args.solver_search else None, symmetry=symmetry)
     else:
         names = args.p or list(elo.model_database.models().keys())
         print(json.dumps(elo.compare_models(*names, num_games=args.games, openings=args.openings,
-                                            record_games=args.record), indent=1, sort_keys=True))
+                                            record_games=args.record, symmetry=symmetry), indent=1, sort_keys=True))
 
 
 if __name__ == "__main__":

@@ -103,8 +103,13 @@ class SelfPlayEngine:
                  opponent_iterations=None, record=True, search_threads=1, leaf_dedup=None, opponent_alpha=None,
                  opponent_strong_play=None, opponent_search_threads=None, eval_cache=None, openings=None,
                  opening_period=0, opponent_depth=2, record_games=False, proof_play=False, opponent_proof_play=None,
-                 proof_stop_every=0, stored_bounds=False, solver_search=False, opponent_solver_search=None):
-        """stored_bounds: keep the score bounds in the nodes (Arena.set_stored_bounds; off by default): games are
+                 proof_stop_every=0, stored_bounds=False, solver_search=False, opponent_solver_search=None,
+                 symmetry=None):
+        """symmetry: "mirror" | None (the default).  With "mirror" every leaf is evaluated in canonical orientation
+        (Arena.set_symmetry; symmetry.py): a position and its mirror image share one row, one peer row and one
+        cache record, and both sides search symmetry.SymmetricNet of their network.  Works with every evaluator,
+        pure or not (the flip does not depend on dedup).  Other games than without it.
+        stored_bounds: keep the score bounds in the nodes (Arena.set_stored_bounds; off by default): games are
         bit-identical, and the proof_play verdict and proof_stop read the root's block instead of walking the tree.
         solver_search: True | "refute" | "proved" | False (the default), the policy's selects read the stored bounds
         (Arena.set_solver_rules; stored bounds come with it): a child proved worse than what a sibling secures draws
@@ -160,6 +165,9 @@ class SelfPlayEngine:
                            leaf_format=self.evaluator.leaf_format, leaf_layout=self.evaluator.leaf_layout,
                            cpuct=cpuct, x_noise=x_noise, alpha=alpha, blocks_per_tree=blocks_per_tree,
                            device=self.device, search_threads=max(k0, k1))
+        self.symmetry = symmetry
+        if symmetry is not None:  # (before any game starts and before a LanedEngine pairs the lanes)
+            self.arena.set_symmetry(symmetry)
         # K sims in flight per tree (the reference's thread_count search, mcts.py:328-331); a search of
         # `budget` sims with k in flight takes ceil(budget / k) network steps
         self.search_threads = self.arena.search_threads
@@ -600,7 +608,7 @@ class LanedEngine:
                  stagger=False, cross_dedup=None, lane_sizes=None, **kw):
         # openings= / opening_period= (SelfPlayEngine): every lane gets the same book and assigns it by its
         # lane-local game ids; proof_play= / opponent_proof_play= / proof_stop_every= / stored_bounds= /
-        # solver_search= / opponent_solver_search= reach every
+        # solver_search= / opponent_solver_search= / symmetry= reach every
         # lane too (a lane's proof_stop is queued on its own stream, after the expand of the step)
         if lanes < 1 or n_games < lanes:
             raise ValueError(f"need 1 <= lanes <= n_games (lanes={lanes}, n_games={n_games})")
@@ -659,6 +667,7 @@ class LanedEngine:
         self.select_steps = self.lanes[0].select_steps
         self.search_threads = self.lanes[0].search_threads
         self.leaf_dedup = self.lanes[0].leaf_dedup
+        self.symmetry = self.lanes[0].symmetry
         self.eval_cache = self.lanes[0].eval_cache
         self.evaluator = self.lanes[0].evaluator
         self.select_timer = self.expand_timer = self.nn_timer = self.tower_timer = None
@@ -934,8 +943,10 @@ class LeagueEngine:
     def __init__(self, game, players, pairings, games_per_pairing=100, seed=0, search_threads=4,
                  dtype=torch.float16, subsequence0=0, device=None, leaf_layout="nhwc", cpuct=4.0, x_noise=0.25,
                  blocks_per_tree=0, openings=None, rng="philox", record_games=False, proof_stop_every=0,
-                 stored_bounds=False):
-        """stored_bounds: the arena keeps the score bounds in the nodes (Arena.set_stored_bounds; for the whole
+                 stored_bounds=False, symmetry=None):
+        """symmetry: "mirror" | None, for the whole arena (Arena.set_symmetry): every network's leaves are evaluated
+        in canonical orientation, so each player searches symmetry.SymmetricNet of its network.
+        stored_bounds: the arena keeps the score bounds in the nodes (Arena.set_stored_bounds; for the whole
         arena, since every tree's expansions maintain them): the same games, the proof_play players' verdicts and
         proof_stop read the root's block.  A player dict's "solver_search": True | "refute" | "proved" lets that
         player's selects read the stored bounds (Arena.set_solver_rules, per tree; stored bounds come with it; a
@@ -999,6 +1010,9 @@ class LeagueEngine:
                                subsequence0=subsequence0, evaluate=True, leaf_format=fmt, leaf_layout=layout,
                                cpuct=cpuct, x_noise=x_noise, blocks_per_tree=blocks_per_tree, device=self.device,
                                search_threads=max(ks))
+        self.symmetry = symmetry
+        if symmetry is not None:
+            a.set_symmetry(symmetry)
         self.search_threads = a.search_threads
         self.select_steps = max([-(-int(p.get("iterations", 100)) // max(1, int(p.get("search_threads", K0))))
                                  for p in mcts] or [0])

@@ -73,7 +73,7 @@ class MCTreeSearch(Policy):
                  batch_size=64, memory_size=200000, min_memory=20000, update_nn=True, starting_state_dict=None,
                  thread_count=4, strong_play=False, q_average=True, alpha=1, env_gen=None, evaluator=None,
                  seed=None, device=None, rng="philox", cpuct=4, x_noise=0.25, threading=False, proof_play=False,
-                 stored_bounds=False, solver_search=False):
+                 stored_bounds=False, solver_search=False, symmetry=None):
         network = network if network is not None else evaluator
         env = env if env is not None else env_gen
         rules = solver_search_rules(solver_search)  # (a bad option raises before anything is built)
@@ -112,6 +112,11 @@ class MCTreeSearch(Policy):
                             strong_play=strong_play, leaf_format=self._evaluator.leaf_format,
                             leaf_layout=self._evaluator.leaf_layout, cpuct=cpuct, x_noise=x_noise, alpha=alpha,
                             device=self.device, search_threads=k)
+        # symmetry="mirror": leaves are evaluated in canonical orientation (Arena.set_symmetry): the search runs
+        # symmetry.SymmetricNet of the network, the same function on a position and on its mirror image
+        self.symmetry = symmetry
+        if symmetry is not None:
+            self._arena.set_symmetry(symmetry)
         # proof_play=True: the move choice drops the moves the tree's own proof rules out (Arena.set_proof_play)
         self.proof_play = bool(proof_play)
         if self.proof_play:
@@ -338,7 +343,7 @@ class MCTreeSearch(Policy):
 @torch.no_grad()
 def analyse_positions(game, network, positions, iterations, search_threads=1, x_noise=0.25, seed=0, alpha=1.0,
                       strong_play=False, cpuct=4.0, player=1, device=None, dtype=torch.float16, rng="philox",
-                      pv_len=0, tree=None, bounds=False, stored_bounds=False, solver_search=False):
+                      pv_len=0, tree=None, bounds=False, stored_bounds=False, solver_search=False, symmetry=None):
     """The search's answer for a batch of positions, each a move sequence from the empty board.
 
     One tree-mode arena of one tree per position: reset(player), one play_action step per ply (a tree whose
@@ -360,7 +365,9 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
     keys.  stored_bounds=True keeps the score bounds in the nodes (Arena.set_stored_bounds): the same outputs, `keep`
     read from the root's stored block, and tree=dict(..., bounds=True) lists the stored entries.
     solver_search=True | "refute" | "proved" searches with the stored bounds (Arena.set_solver_rules; stored bounds
-    come with it): other visit counts, still sound bounds; out["solver_stats"] then holds Arena.solver_stats()."""
+    come with it): other visit counts, still sound bounds; out["solver_stats"] then holds Arena.solver_stats().
+    symmetry="mirror" searches symmetry.SymmetricNet of the network (Arena.set_symmetry): a position and its mirror
+    image then get mirrored answers, priors bit for bit."""
     from .openings import validate_openings
 
     game = game if isinstance(game, str) else game_of_env(game)
@@ -375,6 +382,8 @@ def analyse_positions(game, network, positions, iterations, search_threads=1, x_
                   strong_play=strong_play, leaf_format=ev.leaf_format, leaf_layout=ev.leaf_layout, cpuct=cpuct,
                   x_noise=x_noise, alpha=alpha, device=dev, search_threads=search_threads)
     try:
+        if symmetry is not None:
+            arena.set_symmetry(symmetry)
         if stored_bounds:
             arena.set_stored_bounds()
         if any(rules):

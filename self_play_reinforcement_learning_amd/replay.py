@@ -76,15 +76,34 @@ class DeviceReplay:
         start = (self.head - self.count) % self.max_size
         return (start + torch.arange(self.count, device=self.device)) % self.max_size
 
-    def sample_batch(self, batch_size, generator=None):
+    def _mirror_actions(self):
+        """The action map m of the left-right mirror (symmetry.mirror_actions) for this ring's board: columns on
+        a gravity board (A == W), cells a = x * H + y otherwise."""
+        W, H, A = self.width, self.height, self.n_actions
+        a = torch.arange(A, device=self.device)
+        if A == W:
+            return W - 1 - a
+        if A == W * H:
+            return (W - 1 - a // H) * H + a % H
+        raise ValueError(f"no mirror action map for {A} actions on a {W}x{H} board")
+
+    def sample_batch(self, batch_size, generator=None, mirror=False):
         """Uniform sample without replacement (memory.py:26-30) -> (state int64 [k, W, H],
-        z f32 [k], tree_probs f32 [k, A], q f32 [k]) on the device."""
+        z f32 [k], tree_probs f32 [k, A], q f32 [k]) on the device.
+        mirror=True: each sampled row comes back mirrored with probability 1/2 (the state flipped on the W axis,
+        tree_probs through the action map m; z and q as stored).  The coin flips are drawn from the same generator
+        after the permutation, so mirror=False draws exactly what it always drew."""
         if batch_size > self.count:
             raise ValueError(f"cannot sample {batch_size} rows from {self.count}")
         pick = torch.randperm(self.count, device=self.device, generator=generator)[:batch_size]
         idx = self._order()[pick]
         s = self.state[idx].to(torch.int64).view(batch_size, self.width, self.height)
-        return s, self.z[idx], self.probs[idx], self.q[idx].float()
+        probs = self.probs[idx]
+        if mirror:
+            flip = torch.rand(batch_size, device=self.device, generator=generator) < 0.5
+            s = torch.where(flip[:, None, None], s.flip(1), s)
+            probs = torch.where(flip[:, None], probs[:, self._mirror_actions()], probs)
+        return s, self.z[idx], probs, self.q[idx].float()
 
     def sample(self, batch_size):
         """Memory.sample -> list of Move (dtypes as the reference's records, mcts.py:282-288, :230)."""
@@ -153,28 +172,48 @@ class DeviceReplay:
     def load(self, path):
         self.load_snapshot(torch.load(path, weights_only=True, map_location="cpu"))
 
-    def deduplicate(self, key="state", values=("actual_val", "tree_probs"), named_tuple=None, maxlen=None):
+    def deduplicate(self, key="state", values=("actual_val", "tree_probs"), named_tuple=None, maxlen=None,
+                    symmetric=False):
         """Memory.deduplicate (memory.py:35-94, Deduplicator): rows with identical boards merge into
         one whose z and tree_probs (and q) are the group means; groups keep first-occurrence order.
-        Runs on the device: torch.unique over the int8 board rows + index_add."""
+        Runs on the device: torch.unique over the int8 board rows + index_add.
+        symmetric=True: boards that are equal up to the left-right mirror merge too.  Rows are grouped by the
+        orientation whose int8 row vector is lexicographically smaller (their tree_probs through the action map m),
+        and a group that holds both orientations is stored in that one; a group whose rows all have the same
+        orientation -- a row without a partner -- keeps it."""
         if key != "state":
             raise ValueError("only state-keyed deduplication is supported")
         if self.count == 0:
             return
         order = self._order()
         st = self.state[order]
+        pr = self.probs[order]
+        use_m = None
+        if symmetric:
+            mst = st.view(-1, self.width, self.height).flip(1).reshape(-1, self.cells)
+            first = (st != mst).to(torch.uint8).argmax(dim=1, keepdim=True)  # (equal rows: index 0, not smaller)
+            use_m = (mst.gather(1, first) < st.gather(1, first))
+            st = torch.where(use_m, mst, st)
+            pr = torch.where(use_m, pr[:, self._mirror_actions()], pr)
         uniq, inv = torch.unique(st, dim=0, return_inverse=True)
         g = uniq.shape[0]
         n = torch.zeros(g, dtype=torch.float64, device=self.device).index_add_(
             0, inv, torch.ones(self.count, dtype=torch.float64, device=self.device))
         zs = torch.zeros(g, dtype=torch.float64, device=self.device).index_add_(0, inv, self.z[order].double())
         ps = torch.zeros((g, self.n_actions), dtype=torch.float64, device=self.device).index_add_(
-            0, inv, self.probs[order].double())
+            0, inv, pr.double())
         qs = torch.zeros(g, dtype=torch.float64, device=self.device).index_add_(0, inv, self.q[order])
         first = torch.full((g,), self.count, dtype=torch.int64, device=self.device).scatter_reduce_(
             0, inv, torch.arange(self.count, device=self.device), reduce="amin")
         rank = torch.argsort(first)
-        rows = dict(state=uniq[rank], tree_probs=(ps / n[:, None])[rank].float(), q=(qs / n)[rank],
+        pm = ps / n[:, None]
+        if use_m is not None:  # groups of mirrored rows only go back to their own orientation
+            back = torch.zeros(g, dtype=torch.float64, device=self.device).index_add_(
+                0, inv, use_m.reshape(-1).double()) == n
+            uniq = torch.where(back[:, None],
+                               uniq.view(-1, self.width, self.height).flip(1).reshape(-1, self.cells), uniq)
+            pm = torch.where(back[:, None], pm[:, self._mirror_actions()], pm)
+        rows = dict(state=uniq[rank], tree_probs=pm[rank].float(), q=(qs / n)[rank],
                     q_f64=torch.zeros(g, dtype=torch.uint8, device=self.device), z=(zs / n)[rank].float())
         size = self.max_size if maxlen is None else int(maxlen)
         self.max_size = size

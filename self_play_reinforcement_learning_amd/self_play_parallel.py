@@ -94,7 +94,7 @@ class SelfPlayScheduler:
                  evaluation_network=None, stagger_mem_step=5000, deduplicate=False, update_delay=0.01,
                  self_play=None, n_games=None, device=None, seed=0, updates_per_ply=4, lanes=None, exchange_every=8,
                  gpus=None, start_time=None, overlap_training=False, train_autocast=True, train_graph=True,
-                 train_hip_convs=True):
+                 train_hip_convs=True, symmetry=None, train_mirror=False):
         # constructor arguments, for rank processes started by this scheduler (_run_ranks)
         self._init_kwargs = {k: v for k, v in locals().items() if k not in ("self", "__class__")}
         self.policy_container = policy_container
@@ -129,6 +129,12 @@ class SelfPlayScheduler:
         # the residual blocks' 3x3 convolutions of the autocast update on the HIP matrix-core kernels
         # (trainconv.py) instead of MIOpen (_Trainer hip_convs=True)
         self.train_hip_convs = train_hip_convs
+        # symmetry="mirror": the self-play engine and the evaluation games evaluate every leaf in canonical
+        # orientation (Arena.set_symmetry; None = the policy container's own policy_kwargs["symmetry"]).
+        # train_mirror=True: the trainer's batches come back mirrored with probability 1/2 per row
+        # (DeviceReplay.sample_batch(mirror=True)) and the epoch-end deduplicate() merges mirror images
+        self.symmetry = symmetry
+        self.train_mirror = bool(train_mirror)
         self.exchange_every = exchange_every  # plies per episode-batch exchange round (distributed.MoveExchange)
         # >1: LanedEngine (arenas on separate HIP streams, each a complete arena); None = 2 lanes for
         # arenas of >= 1,024 games, where the overlap pays (bench.py), else one arena
@@ -170,6 +176,9 @@ class SelfPlayScheduler:
         kw = dict(self.policy_container.policy_kwargs)
         return kw
 
+    def _symmetry(self):
+        return self.symmetry if self.symmetry is not None else self._policy_kwargs().get("symmetry")
+
     def _resolve_threads(self, inference_proxy=True):
         """Simulations in flight per tree, resolved in one place for self-play and evaluation
         games: the reference's workers search with thread_count threads + virtual loss exactly when
@@ -195,7 +204,8 @@ class SelfPlayScheduler:
         ekw = dict(iterations=kw.get("iterations", 100), alpha=kw.get("alpha", 1),
                    strong_play=kw.get("strong_play", False), seed=self.seed + 7919 * self.rank, device=self.device,
                    search_threads=max(1, threads), proof_play=bool(kw.get("proof_play", False)),
-                   stored_bounds=bool(kw.get("stored_bounds", False)), solver_search=kw.get("solver_search", False))
+                   stored_bounds=bool(kw.get("stored_bounds", False)), solver_search=kw.get("solver_search", False),
+                   symmetry=self._symmetry())
         lanes = self.lanes if self.lanes is not None else (2 if n_games >= 1024 else 1)
         if lanes > 1 and n_games >= 2 * lanes:
             self.engine = LanedEngine(self.game, self.network, n_games=n_games, lanes=lanes, **ekw)
@@ -212,7 +222,7 @@ class SelfPlayScheduler:
                                 batch_size=kw.get("batch_size", 64), min_memory=kw.get("min_memory", 20000),
                                 q_average=kw.get("q_average", True), device=self.device, W=self.W, H=self.H,
                                 A=self.A, overlap=self._overlap_ok(), autocast=self.train_autocast,
-                                graph=self.train_graph, hip_convs=self.train_hip_convs)
+                                graph=self.train_graph, hip_convs=self.train_hip_convs, mirror=self.train_mirror)
         if self.save_dir and self.rank == 0:  # rank 0 owns the replay ring (MoveExchange gathers to it)
             self.trainer.run_dir = os.path.join(self.save_dir, self.start_time)
         if resume_memory and self.rank == 0:  # updateworker.py:67-69 (before the model, as there)
@@ -393,7 +403,10 @@ class SelfPlayScheduler:
                 # that raises TypeError (memory.py:93: the rebuilt tuple lacks q) and, caught, skips the
                 # checkpoint.  The device ring merges duplicate boards (z, tree_probs and q averaged);
                 # its (state, z, tree_probs) part is pinned by G7 (tests/test_memory_golden.py)
-                self.trainer.memory.deduplicate()
+                if self.train_mirror:
+                    self.trainer.memory.deduplicate(symmetric=True)
+                else:
+                    self.trainer.memory.deduplicate()
             self.trainer.save_memory()  # updateworker.py:92, after stagger / dedup (:86-89)
             reward = self.evaluate_policy(epoch)
             self.trainer.lr_step(reward)
@@ -439,7 +452,8 @@ class SelfPlayScheduler:
                               # (the bounds are kept for the whole arena: either side's stored_bounds switches them on)
                               stored_bounds=bool(kw.get("stored_bounds", False) or okw.get("stored_bounds", False)),
                               solver_search=kw.get("solver_search", False),
-                              opponent_solver_search=okw.get("solver_search", False), **opp_kw), per_rank
+                              opponent_solver_search=okw.get("solver_search", False), symmetry=self._symmetry(),
+                              **opp_kw), per_rank
 
     def _play_evaluation(self, n_games, openings=None, records=None):
         """n_games evaluation games over all ranks (task i -> swap_sides = i odd, update=False);
@@ -576,8 +590,12 @@ class _Trainer:
     GRAPH_WARMUP = 3
 
     def __init__(self, network, optim, memory_size, batch_size, min_memory, q_average, device, W=7, H=6, A=7,
-                 train_mode=True, overlap=True, autocast=False, graph=True, hip_convs=True):
+                 train_mode=True, overlap=True, autocast=False, graph=True, hip_convs=True, mirror=False):
         from .replay import DeviceReplay
+
+        # mirror: every sampled row mirrored with probability 1/2 (DeviceReplay.sample_batch(mirror=True)); the
+        # graphed step takes its batch as an input, so the capture is the same
+        self._sample_kw = {"mirror": True} if mirror else {}
 
         dev = torch.device(device) if device is not None else torch.device("cpu")
         self.stream = torch.cuda.Stream(device=dev) if overlap and dev.type == "cuda" else None
@@ -659,12 +677,12 @@ class _Trainer:
         self.steps += 1
         if self.stream is None:
             if self.graph:
-                self.last_loss = self._step_graphed(*self.memory.sample_batch(self.batch_size))
+                self.last_loss = self._step_graphed(*self.memory.sample_batch(self.batch_size, **self._sample_kw))
                 return float(self.last_loss)
-            return self.train_batch(*self.memory.sample_batch(self.batch_size))
+            return self.train_batch(*self.memory.sample_batch(self.batch_size, **self._sample_kw))
         self.stream.wait_stream(torch.cuda.current_stream(self.stream.device))
         with torch.cuda.stream(self.stream):
-            batch = self.memory.sample_batch(self.batch_size)
+            batch = self.memory.sample_batch(self.batch_size, **self._sample_kw)
             self.last_loss = self._step_graphed(*batch) if self.graph else self._train_step(*batch)
         return self.last_loss
 
