@@ -536,7 +536,7 @@ __device__ bool set_node(const View &v, int tree, int a) {
     int64_t *cnt = v.cnt + (size_t)tree * C_NCNT;
     cnt[C_SETNODE] += 1;
     if (done) {
-      const double val = terminal_value(v, tree, Board{v.rpos[tree], v.rneg[tree]}, rew * rp);
+      const double val = terminal_value(v.tstrong[tree] != 0, Board{v.rpos[tree], v.rneg[tree]}, rew * rp);
       nd_n<P>(v, nb + child) = 1;
       nd_w<P>(v, nb + child) = nd_w<P>(v, nb + child) + val;
       if (v.tstrong[tree]) nd_f<P>(v, nb + child) = 1;

@@ -73,16 +73,9 @@ __device__ __forceinline__ bool tree_idle(const View &v, int tree) {
   return !busy;
 }
 
-// terminal value of _expand_node (mcts.py:305-313) for `tree`'s own strong_play; r = reward * mover
+// terminal value of _expand_node (mcts.py:305-313) for the tree's own strong_play; r = reward * mover
 __device__ __forceinline__ double terminal_value(bool strong, Board parent, int r) {
   if (strong) {
-    const int num_steps = popc(parent.pos | parent.neg) + 1;  // np.sum(np.abs(state)) + 1
-    return (1.18 - ((double)(9 * num_steps) / 350.0)) * (double)r;
-  }
-  return (double)r;
-}
-__device__ __forceinline__ double terminal_value(const View &v, int tree, Board parent, int r) {
-  if (v.tstrong[tree]) {
     const int num_steps = popc(parent.pos | parent.neg) + 1;  // np.sum(np.abs(state)) + 1
     return (1.18 - ((double)(9 * num_steps) / 350.0)) * (double)r;
   }
@@ -367,7 +360,8 @@ __device__ __forceinline__ void group_argmax_carry(double &s, int &idx, int &c0,
 
 // the same with a fourth int payload (the SB = true selects carry the winner's stored bounds).  A copy on purpose,
 // not a variadic payload under both: the SB = false kernels keep calling group_argmax_carry as it stood, so their
-// code stays the parent's instruction for instruction; a change to the comparison must be made in both
+// code stays the parent's instruction for instruction; a change to the comparison must be made in both.  (One
+// variadic step under both was tried again later, a fold over the payload: every search kernel changed throughout)
 template <int CTRL>
 __device__ __forceinline__ void argmax_carry4_step(double &s, int &idx, int &c0, int &c1, int &c2, int &c3, double &d0) {
   const double so = dpp_d<CTRL>(s), d0o = dpp_d<CTRL>(d0);
@@ -536,7 +530,7 @@ __global__ __launch_bounds__(64) void k_select(View v, int n_active) {
         if (done) {
           // terminal: value r (or strong_play shaping), no children, backup in place
           const bool strong = v.tstrong[tree] != 0;
-          const double val = proved ? sb_proved_value<G>(strong, s_a, player) : terminal_value(v, tree, b, rew * player);
+          const double val = proved ? sb_proved_value<G>(strong, s_a, player) : terminal_value(strong, b, rew * player);
           for (int k = 0; k <= depth; ++k) {
             const size_t idx = nb + s_node[grp][k];
             nd_n<P>(v, idx) = s_n[grp][k] + 1;
